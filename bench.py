@@ -1,10 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the quantized MemN2N inference hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--full] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path (all hops of every query, then the answer layer) over
 one resident batch of synthetic queries.  Prints ONE JSON line (rank 0).
+
+A plain run sets up, runs W warm-up steps and K timed steps of one workload and prints its line: nothing else.
+`--full` adds everything beyond the headline figure: the secondary configs under `configs` (below), the >= 2 s
+sustained window, the CPU baselines, and (babi_task1_*) the host-input copy / pipelined / 64-story serving legs.
+`--dump-outputs DIR` writes what the timed path returned in its last timed step as DIR/<name>.npy (see dump_outputs).
 
 Workloads (config.workload; `--workload NAME` runs one alone):
   synth10k_d128_q25  BASELINE.json configs[3] EXACTLY as SURVEY.md 8(d) words it, one GPU's shard: |memory| = 10 000 slots,
@@ -12,7 +17,7 @@ Workloads (config.workload; `--workload NAME` runs one alone):
                   answer matrix [256][128] (the MFMA projection), 3 hops, fixed-point dot attention (ATTENTION_MODE 2),
                   8 192 queries per GPU, per-query memories (62.9 GB).  Default: this is the configuration the north-star
                   roofline target is quoted on.
-The DEFAULT line (no --workload) carries, beside that headline, one object per BASELINE.json config under `configs`
+The DEFAULT line (no --workload) of a --full run carries, beside that headline, one object per BASELINE.json config under `configs`
 (each: value, ms_per_step, roofline or "QPS only" as SURVEY.md 8(d) says, cpu_baseline) -- all under the driver's clock:
   mem50     babi_mem50             |memory| = 50 (MAX_SEN_LEN cap), D = 60: the size BASELINE.json's metric string names
                                    (also promoted to top-level keys mem50_queries_per_s / mem50_roofline_frac)
@@ -144,6 +149,39 @@ def shard_report(out, pred, B, rank, world, dev):
     m = torch.stack(parts).cpu().numpy()
     out["shards"] = [[int(a), int(b)] for a, b, _ in m]
     out["pred_crc32"] = [int(c) for _, _, c in m]
+
+
+DUMP_BYTES_MAX = 60_000_000     # --dump-outputs: under 64 MB in all, the .npy headers included
+
+
+def keep_outputs(args, res, outputs):
+    """--dump-outputs: attach what the last timed step returned to its caller (device tensors; main() writes them)"""
+    if args.dump_outputs:
+        res["_outputs"] = {k: v for k, v in outputs.items() if v is not None}
+
+
+def dump_outputs(directory, outputs):
+    """DIR/<name>.npy per output: float tensors as float32, integer ones as float64 (exact).  Inputs are seeded, so two builds
+    run with the same arguments can be compared file by file.  Above DUMP_BYTES_MAX the arrays that have one row per query
+    keep a fixed, seeded sample of rows (the same for the same batch size), whose indices go to DIR/sample_rows.npy."""
+    d = Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+    arrs = {}
+    for k, t in outputs.items():
+        a = t.detach().cpu().numpy()
+        arrs[k] = a.astype(np.float32 if a.dtype.kind == "f" and a.itemsize <= 4 else np.float64)
+    n = max((a.shape[0] for a in arrs.values() if a.ndim), default=0)
+    per_query = [k for k, a in arrs.items() if a.ndim and a.shape[0] == n]
+    total = sum(a.nbytes for a in arrs.values())
+    if total > DUMP_BYTES_MAX:
+        fixed = total - sum(arrs[k].nbytes for k in per_query)
+        row_bytes = sum(arrs[k].nbytes for k in per_query) // n + 8
+        rows = np.sort(np.random.default_rng(0x5EED).choice(n, (DUMP_BYTES_MAX - fixed) // row_bytes, replace=False))
+        for k in per_query:
+            arrs[k] = arrs[k][rows]
+        arrs["sample_rows"] = rows.astype(np.float64)
+    for k, a in arrs.items():
+        np.save(d / f"{k}.npy", np.ascontiguousarray(a))
 
 
 def _round(x, sig=6):
@@ -440,11 +478,12 @@ def run_bow(args, name, wl, net, cfg, wts, hm, dev, rank, world, model):
                      "frac": bytes_in * args.steps / elapsed / 1e9 / HBM_PEAK_GBS, "traffic": None},
         "accuracy_note": "random weights: predictions are compared with the oracle, not with labels",
     }
+    keep_outputs(args, res, out)
     shard_report(res, out["pred"], B, rank, world, dev)
     # the batched API takes device pointers; when the host owns the stories, one bulk H2D copy per batch
     # (cuda_data_in's role, lib/layer_cuda.cu:3960-4035) precedes it.  Measured from pinned memory, serial
-    # with the compute (no overlap): reported beside `value`, never as `value`.
-    if rank == 0:
+    # with the compute (no overlap): reported beside `value`, never as `value`.  (--full only)
+    if rank == 0 and args.full:
         srcs = [t.cpu().pin_memory() for t in ((sw, qw) if use_idx else (story, ques))] + [row_off.cpu().pin_memory(), ans.cpu().pin_memory()]
         dsts = [torch.empty_like(t, device=dev) for t in srcs]
         torch.cuda.synchronize()
@@ -606,6 +645,7 @@ def run_joint(args, name, wl, cfg, wts, hm, dev, rank, world, model):
                      "frac": bytes_in * args.steps / elapsed / 1e9 / HBM_PEAK_GBS, "traffic": None},
         "accuracy_note": "random weights: predictions are compared with the oracle, not with labels",
     }
+    keep_outputs(args, res, dict(zip(("pred", "cost", "match"), out)))
     shard_report(res, out[0], B, rank, world, dev)
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         V, dd = cfg["dim_input"], int(g["dim_dict"])
@@ -689,6 +729,7 @@ def run_trained(args, name, wl, dev, rank, world, model, abi, replicate_model):
                      "reference_run": {k: rec[k] for k in ("binary", "argv", "verify_line", "train_error_first_epoch", "train_error_last_epoch", "epochs")},
                      "chance_error": 5.0 / 6.0},
     }
+    keep_outputs(args, res, dict(zip(("pred", "cost", "match"), out)))
     shard_report(res, out[0], B, rank, world, dev)
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         offs = ds["row_off"].astype(np.int64)
@@ -706,14 +747,21 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default=None, choices=sorted(WORKLOADS),
-                    help="one workload alone (default: synth10k_d128_q25 as the headline + every BASELINE config under `configs`)")
+                    help="one workload alone (default: synth10k_d128_q25 as the headline; with --full + every BASELINE config under `configs`)")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline figure: secondary configs, sustained window, CPU baselines, host-input and serving legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32 / float64, <= 64 MB in all)")
     ap.add_argument("--secondary-cpu-s", type=float, default=1.2, help="CPU-baseline seconds per leg for the secondary configs")
     ap.add_argument("--queries", type=int, default=0, help="queries per GPU (default: the workload's)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="default line: the headline workload only")
-    ap.add_argument("--no-sustained", action="store_true", help="skip the second, longer timing window")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baselines")
+    ap.add_argument("--no-secondary", action="store_true", help="(--full) default line: the headline workload only")
+    ap.add_argument("--no-sustained", action="store_true", help="(--full) skip the second, longer timing window")
     ap.add_argument("--sustain-s", type=float, default=2.0, help="length of the sustained window in seconds (default 2)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if not args.full:                   # a plain run: set-up, warm-up, the timed steps, the line -- nothing else
+        args.no_cpu_baseline = args.no_secondary = args.no_sustained = True
+    return args
 
 
 def free_port():
@@ -807,6 +855,9 @@ def main(argv=None):
         default_line = args.workload is None
         name = args.workload or HEADLINE
         out = run_workload(args, name, dev, rank, world)
+        outputs = out.pop("_outputs", None)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, outputs)
         # BASELINE.json quotes its metric at |mem| = 50 (the bAbI cap) and sets its target at |mem| = 10 000: the default
         # line's `value` is the 10 000-slot configuration; beside it, under `configs`, one object per BASELINE.json config
         # (SECONDARY above), all timed inside this one driver-clocked run; the |mem| = 50 figures are top-level keys too
@@ -818,7 +869,7 @@ def main(argv=None):
                 torch.cuda.empty_cache()
                 # (--queries, when given, caps every workload of the line: small rehearsals of the whole line)
                 a2 = argparse.Namespace(**{**vars(args), "queries": min(args.queries, WORKLOADS[wname]["B"]) if args.queries else 0,
-                                           "no_sustained": args.no_sustained or not sus, "sustain_s": 1.0})
+                                           "no_sustained": args.no_sustained or not sus, "sustain_s": 1.0, "dump_outputs": None})
                 try:
                     sec = run_workload(a2, wname, dev, rank, world)
                 except Exception as e:                             # one config failing must not cost the line its other five
@@ -1013,6 +1064,10 @@ def run_workload(args, name, dev, rank, world):
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    # what the caller gets: the final controller state u and the predictions (answer_i8's logits are its workspace)
+    step_outputs = {"u": u, "pred": pred}
+    if args.dump_outputs:                                             # (u's buffer is written again by the sustained window)
+        step_outputs = {k: v.clone() for k, v in step_outputs.items()}
 
     hop_ms = float(np.mean([e[0].elapsed_time(e[1]) for e in ev]))    # dominant kernel, HIP events
     ans_ms = float(np.mean([e[1].elapsed_time(e[2]) for e in ev]))
@@ -1130,6 +1185,7 @@ def run_workload(args, name, dev, rank, world):
     if st:
         out["ranks"] = st
     with_bcast(out, bcast)
+    keep_outputs(args, out, step_outputs)
     shard_report(out, pred, B, rank, world, dev)
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         pool = mem_pool(cfg, keys, vals, u0, S, D)

@@ -3,15 +3,21 @@ fixtures the reference's OWN sample.c produced (tests/golden/*_words.npz, made b
 oracle/_ref): same dictionary, same dimensions, and for every sentence / question the same bag of words, the same time
 entry, the same answer index.  Host-only: no GPU needed."""
 import re
-from pathlib import Path
 
 import numpy as np
 import pytest
 
 from conftest import GOLD, load_pkg
 
-DATA = Path("/root/reference/MemN2N/dataset")
-needs_reference = pytest.mark.skipif(not DATA.exists(), reason="the reference's dataset files live in /root/reference")
+
+def parsed_sets(name, out_dir):
+    """the reference's parsed bAbI record files (its MemN2N/dataset/en_*_parsed), kept byte for byte as one uint8 array per
+    file in tests/golden/babi_parsed/<name>.npz (en_10k_qa1: task 1 of en_10k; en_1k: all 40 files of en_1k), written out
+    under out_dir; returns out_dir"""
+    g = np.load(GOLD / "babi_parsed" / f"{name}.npz")
+    for f in g.files:
+        (out_dir / f).write_bytes(g[f].tobytes())
+    return out_dir
 
 
 @pytest.fixture(scope="module")
@@ -42,18 +48,18 @@ def compare_with_fixture(ds, g):
     np.testing.assert_array_equal(np.where(mine == 0xFFFFFFFF, 0xFF, mine), fa)
 
 
-@needs_reference
-def test_qa1_test_set_equals_the_reference_vectorisation(abi):
-    sub = DATA / "en_10k_parsed"
+def test_qa1_test_set_equals_the_reference_vectorisation(abi, tmp_path):
+    sub = parsed_sets("en_10k_qa1", tmp_path)
     ds = abi.load_dataset(sub / "qa1_single-supporting-fact_train_set", sub / "qa1_single-supporting-fact_test_set", 50)
     compare_with_fixture(ds, np.load(GOLD / "babi_qa1_test1000_words.npz"))
     # sentence order is kept (the fixture only knows bags of words): "John travelled to the hallway" -> 5 words + time
     assert (ds["story_words"][0] != 0xFFFF).sum() == 6 and ds["dim_word"] == 7
 
 
-@needs_reference
 def test_joint_20_tasks_equal_the_reference_vectorisation(abi, tmp_path):
-    sub = DATA / "en_1k_parsed"
+    sub = tmp_path / "en_1k_parsed"
+    sub.mkdir()
+    parsed_sets("en_1k", sub)
     tasks = sorted({re.sub(r"_(train|test)_set$", "", f.name) for f in sub.iterdir()}, key=lambda t: int(re.match(r"qa(\d+)_", t).group(1)))
     assert len(tasks) == 20
     for kind in ("train", "test"):                                  # the 20 files back to back, as oracle/gen_golden.py builds them

@@ -366,7 +366,7 @@ def test_bench_default_line_with_two_ranks_rehearsal():
     """the WHOLE default line (headline + every BASELINE config under `configs`) with two ranks on this box's one GPU
     (QMANN_BENCH_REHEARSE=1, small batches): every workload builds its model on rank 0, broadcasts the quantised blob and runs on
     both ranks; the line keeps its shape -- what the driver's N > 1 runs will print"""
-    two = _bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--queries", "2048", "--no-sustained"], QMANN_BENCH_REHEARSE="1")
+    two = _bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--queries", "2048", "--no-sustained", "--full"], QMANN_BENCH_REHEARSE="1")
     assert two["n_gpus"] == 2 and two["config"]["workload"] == "synth10k_d128_q25"   # config 4 as SURVEY 8(d) words it
     assert sorted(two["configs"]) == ["cfg2", "cfg3", "cfg4_q52", "cfg5", "mem50"]
     assert "1 000" in two["configs"]["cfg2"]["data"]                  # config 2 on the whole qa1 test set

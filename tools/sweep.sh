@@ -8,5 +8,4 @@ r=d.get("roofline",{})
 print("$w", round(d["value"]/1e6,3), "Mq/s", round(d["ms_per_step"],4), "ms/step kernel_ms", r.get("kernel_ms"), "frac", r.get("frac") and round(r["frac"],4), "ans", d.get("answer_layer",{}).get("ms"), d.get("pcie_inclusive") or d.get("h2d") or "")
 PY
 done
-timeout -k 10 300 python bench.py > gpurun_out/sw_default.log 2>&1
-tail -1 gpurun_out/sw_default.log | cut -c1-300
+timeout -k 10 300 python bench.py --full 2>&1 | tail -1 | cut -c1-300
