@@ -166,7 +166,7 @@ int qmann_hops_packed(const qmann_net *net, const uint64_t *key_planes, size_t k
  * Arithmetic.  qmann_answer_f32_serial sums every logit over the embedding axis serially in float, separate multiply and add:
  * the reference's own order (lib/layer_cuda.cu:70-80), bit-equal logits; e^x through expf, a double total, the quotient of the
  * double division (:2006-2042).  qmann_answer_f32 takes, at the bAbI shapes (dim_emb <= 64, dim_input <= 256, e^x / 2^x base),
- * the FUSED form on the bf16 matrix cores instead (csrc/batch_io.hip::k_answer_mfma): u -- which must lie on an 8-bit grid, as
+ * the FUSED form on the bf16 matrix cores instead (csrc/batch_answer.hip::k_answer_mfma): u -- which must lie on an 8-bit grid, as
  * the hop kernels write it -- times W split exactly into three bf16 parts, float accumulation, hardware 2^x; closer to the
  * exact sum than the serial float loop, and within north_star's 1e-5 of it on the probabilities (absolute; relative 1e-5 while
  * |logit| <= 16, where a unit in the last place of a logit is still below 1e-6); predictions agree wherever the two best

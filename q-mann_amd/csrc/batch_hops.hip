@@ -28,6 +28,7 @@
 //
 // All integer work is exact; the only floating-point step is the softmax table.
 #include "hops_mid.h"
+#include "hops_host.h"
 
 namespace {
 
@@ -180,8 +181,6 @@ __global__ void k_quantize_i8(const float *__restrict__ src, int8_t *__restrict_
     }
 }
 
-inline bool fmt8(qmann_fmt f) { return f.iwl + f.frac >= 1 && f.iwl + f.frac <= 7; }
-
 // qmann_check_slots: how many stories exceed the caller's bound (and would be cut by the hop kernels)
 __global__ void k_check_slots(const uint32_t *__restrict__ row_off, uint32_t n_query, uint32_t max_slots, uint32_t *n_over)
 {
@@ -240,13 +239,13 @@ int qmann_quantize_i8(const float *src, int8_t *dst, size_t rows, uint32_t cols,
 {
     QmBatched qm_scope;
     if (!src || !dst || pitch < cols) return QMANN_EINVAL;
-    if (!fmt8(fmt)) return QMANN_ERANGE;
+    if (!qm_fmt8(fmt)) return QMANN_ERANGE;
     if (layout != QMANN_CODE_TWOS && layout != QMANN_CODE_SIGNMAG) return QMANN_EINVAL;
     const size_t n = rows * pitch;
     if (n == 0) return QMANN_OK;
     const size_t blocks = (n + 255) / 256;
     k_quantize_i8<<<(unsigned)(blocks < 262144 ? blocks : 262144), 256, 0, (hipStream_t)stream>>>(src, dst, rows, cols, pitch,
-                                                                              QFmt{fmt.iwl, fmt.frac}, layout);
+                                                                              qm_qfmt(fmt), layout);
     QM_LAUNCH_CHECK();
     return qm_scope.rc();
 }
@@ -256,89 +255,38 @@ int qmann_hops_i8(const qmann_net *net, const int8_t *keys, const int8_t *vals, 
                   const qmann_taps *taps, uint32_t n_query, void *stream)
 {
     QmBatched qm_scope;
-    if (!net || !keys || !vals || !row_off || !u0 || !u_out) return QMANN_EINVAL;
-    if (net->n_hop == 0 || net->n_hop > QMANN_MAX_HOP) return QMANN_EINVAL;
-    if (net->dim_emb == 0 || net->dim_emb > net->dim_emb_pad) return QMANN_EINVAL;
-    if (net->dim_emb_pad != 64 && net->dim_emb_pad != 128 && net->dim_emb_pad != 256) return QMANN_EUNSUPPORTED;
+    if (const int rc = check_hop_call(net, keys, vals, row_off, u0, u_out)) return rc;
     if (taps && hop_stride == 0) return QMANN_EINVAL;       // taps are indexed [hop][row]: they need distinct hop planes
     if (net->attention_mode == QMANN_ATT_APPX)
         return qmann_hops_appx_impl(net, keys, vals, hop_stride, row_off, max_slots, u0, u_out, taps, n_query, stream);
     if (net->attention_mode == QMANN_ATT_HAMMING_V0 || net->attention_mode == QMANN_ATT_HAMMING_V1)
         return qmann_hops_hambytes_impl(net, keys, vals, hop_stride, row_off, max_slots, u0, u_out, taps, n_query, stream);
     if (net->attention_mode != QMANN_ATT_FIXED && net->attention_mode != QMANN_ATT_FLOAT) return QMANN_EUNSUPPORTED;
-    if (net->softmax_base > QMANN_SOFTMAX_EXP_PLAN) return QMANN_EINVAL;
-    if (!fmt8(net->bin) && net->bin.iwl + net->bin.frac != 0) return QMANN_ERANGE;     // (0,0) = BINARY_MODE: u binarised
-    for (uint32_t h = 0; h < net->n_hop; h++) {
-        if (!fmt8(net->act[h]) || !fmt8(net->w[h]) || !fmt8(net->att[h])) return QMANN_ERANGE;
-        if (net->en_lin_map && !net->lin_map[h]) return QMANN_EINVAL;
-    }
+    HopArgs a;
+    if (const int rc = fill_hop_args(a, net, keys, vals, hop_stride, hop_stride, row_off, u0, u_out, taps)) return rc;
+    a.max_slots = max_slots;
     const size_t lds = qmann_hops_lds_bytes(max_slots);
     if (lds > 160 * 1024 - 1024) return QMANN_ERANGE;   // a little static LDS is used besides
     if (n_query == 0) return QMANN_OK;
-    if (n_query >= (1u << 24)) return QMANN_ERANGE;      // one workgroup per query: a launch holds < 2^32 threads
-
-    HopArgs a{};
-    a.keys = keys; a.vals = vals; a.hop_stride = hop_stride; a.key_hop_stride = hop_stride;
-    a.row_off = row_off; a.u0 = u0; a.u_out = u_out;
-    if (taps) {
-        a.tap_codes = taps->score_codes; a.tap_scores = taps->scores; a.tap_probs = taps->probs;
-        a.tap_o = taps->o; a.tap_u = taps->u;
-    }
-    a.rows_total = hop_stride ? (uint32_t)(hop_stride / net->dim_emb_pad) : (uint32_t)qm_rows_hint;      // (tied hops: the caller's hint, or 0 = unknown)
-    a.max_slots = max_slots;
-    a.n_hop = net->n_hop; a.D = net->dim_emb; a.Dp = net->dim_emb_pad;
-    a.softmax_base = net->softmax_base; a.en_lin_map = net->en_lin_map;
-    a.softmax_shift = net->softmax_shift_based; a.en_att_scale = net->en_att_scale; a.en_non_lin = net->en_non_linearity;
-    for (uint32_t h = 0; h < net->n_hop; h++) {
-        a.att_scale[h] = net->att_scale[h];
-        a.lin_map[h] = net->lin_map[h];
-        a.act[h] = QFmt{net->act[h].iwl, net->act[h].frac};
-        a.w[h] = QFmt{net->w[h].iwl, net->w[h].frac};
-        a.att[h] = QFmt{net->att[h].iwl, net->att[h].frac};
-    }
-    a.bin = QFmt{net->bin.iwl, net->bin.frac};
+    if (qm_too_many_queries(n_query)) return QMANN_ERANGE;
 
     if (net->attention_mode == QMANN_ATT_FLOAT)
         return qmann_hops_float_impl(a, net->dim_emb_pad, max_slots, n_query, stream);
 
     hipStream_t st = (hipStream_t)stream;
-    if (lean_supported(a, max_slots, 64)) {                 // hops_lean.h
-        launch_lean<kModeFixed, 8>(a, max_slots, n_query, st);
-        QM_LAUNCH_CHECK();
-        return qm_scope.rc();
-    }
-    if (max_slots <= (uint32_t)kWave) {                     // hops_small.h
-        if (net->dim_emb_pad == 64) k_hops_small<4, 4, kModeFixed, 8><<<n_query, kWave, 0, st>>>(a, 64);
-        else if (net->dim_emb_pad == 128) k_hops_small<8, 8, kModeFixed, 8><<<n_query, kWave, 0, st>>>(a, 128);
-        else k_hops_small<16, 16, kModeFixed, 8><<<n_query, kWave, 0, st>>>(a, 256);
-        QM_LAUNCH_CHECK();
-        return qm_scope.rc();
-    }
-    if (mid_supported(a, max_slots)) {                      // hops_mid.h: 65 .. 1 024 slots at bAbI width
-        launch_mid(a, max_slots, n_query, st);
-        QM_LAUNCH_CHECK();
-        return qm_scope.rc();
-    }
-    // memories of 65..256 slots run one wavefront per query with the histogram softmax: four times
-    // as many queries resident per CU and no cross-wavefront barriers
-    const dim3 grid(n_query), block(max_slots <= 256 ? kWave : kBlock);
-#define QM_LAUNCH_HOPS_W(LPR, UN, NT, MINW, W7)                                                         \
-    do {                                                                                                \
-        if (lds > kLdsDefaultLimit)         /* beyond the default 64 KB: raise the limit (no cached state:  */ \
-            QM_HIP(hipFuncSetAttribute((const void *)k_hops_fixed<LPR, UN, NT, MINW, W7>, /* thread- and  */ \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); /* device-safe */ \
-        k_hops_fixed<LPR, UN, NT, MINW, W7><<<grid, block, lds, st>>>(a);                               \
-    } while (0)
-#define QM_LAUNCH_HOPS(LPR, UN, NT, MINW)                                                               \
-    do { if (w7) QM_LAUNCH_HOPS_W(LPR, UN, NT, MINW, true); else QM_LAUNCH_HOPS_W(LPR, UN, NT, MINW, false); } while (0)
     bool w7 = !qm_tuning().no_w7;
     for (uint32_t h = 0; h < net->n_hop; h++) w7 = w7 && net->att[h].iwl + net->att[h].frac == 7;
-    // (bounding the kernel to 96 VGPRs for a fifth wavefront per SIMD measured 1-3 % slower: MINW stays 1)
-    if (net->dim_emb_pad == 64) QM_LAUNCH_HOPS(4, kUnrollDefault, true, 1);
-    else if (net->dim_emb_pad == 256) QM_LAUNCH_HOPS(16, kUnrollDefault, true, 1);
-    else QM_LAUNCH_HOPS(8, kUnrollDefault, true, 1);
-#undef QM_LAUNCH_HOPS
-#undef QM_LAUNCH_HOPS_W
+    qm_dispatch<4, 8, 16>(net->dim_emb_pad / 16, [&](auto lpr) {
+        constexpr int LPR = decltype(lpr)::value;
+        launch_hops<kModeFixed, 8, LPR, LPR>(a, max_slots, n_query, st, [&] {
+            if (mid_supported(a, max_slots)) { launch_mid(a, max_slots, n_query, st); return; }      // hops_mid.h: 65 .. 1 024 slots at bAbI width
+            // memories of 65..256 slots run one wavefront per query with the histogram softmax: four times
+            // as many queries resident per CU and no cross-wavefront barriers
+            const dim3 block(max_slots <= 256 ? kWave : kBlock);
+            // (bounding the kernel to 96 VGPRs for a fifth wavefront per SIMD measured 1-3 % slower: MINW stays 1)
+            qm_dispatch<false, true>(w7, [&](auto w) { qm_launch(k_hops_fixed<LPR, kUnrollDefault, true, 1, decltype(w)::value>, n_query, block, lds, st, a); });
+        });
+    });
     QM_LAUNCH_CHECK();
     return qm_scope.rc();
 }

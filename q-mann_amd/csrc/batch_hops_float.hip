@@ -207,15 +207,6 @@ k_hops_float(const HopArgs a)
     if (tid < D) a.u_out[(size_t)q * D + tid] = relu_if(u_f[tid], a.en_non_lin != 0);
 }
 
-template <int LPR>
-void launch_float(const HopArgs &a, size_t lds, uint32_t n_query, hipStream_t st)
-{
-    if (lds > kLdsDefaultLimit)
-        QM_HIP(hipFuncSetAttribute((const void *)k_hops_float<LPR>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)lds));
-    k_hops_float<LPR><<<n_query, kBlock, lds, st>>>(a);
-}
-
 }  // namespace
 
 extern "C" int qmann_hops_float_impl(const HopArgs &a, uint32_t Dp, uint32_t max_slots, uint32_t n_query, void *stream)
@@ -225,9 +216,7 @@ extern "C" int qmann_hops_float_impl(const HopArgs &a, uint32_t Dp, uint32_t max
     const size_t lds = (size_t)kOffScores + (((size_t)max_slots * 4 + 15) & ~(size_t)15);
     if (lds > 160 * 1024 - 1024) return QMANN_ERANGE;
     hipStream_t st = (hipStream_t)stream;
-    if (Dp == 64) launch_float<4>(a, lds, n_query, st);
-    else if (Dp == 128) launch_float<8>(a, lds, n_query, st);
-    else launch_float<16>(a, lds, n_query, st);
+    qm_dispatch<4, 8, 16>(Dp / 16, [&](auto lpr) { qm_launch(k_hops_float<decltype(lpr)::value>, n_query, kBlock, lds, st, a); });
     QM_LAUNCH_CHECK();
     return qm_scope.rc();
 }

@@ -23,7 +23,7 @@
 // so they are kept as int16 in LDS.  V0 evaluates the softmax once per distinct count (histogram),
 // the other modes per slot (max, sum of exp in double, quotient), as lib/layer_cuda.cu:1969-2060 does.
 #include "ham_common.h"
-#include "hops_lean.h"
+#include "hops_host.h"
 
 namespace {
 
@@ -275,62 +275,36 @@ k_pack_planes(const uint8_t *__restrict__ sm, uint64_t *__restrict__ planes, siz
     }
 }
 
-inline bool fmt8(qmann_fmt f) { return f.iwl + f.frac >= 1 && f.iwl + f.frac <= 7; }
-
-int fill_args(HopArgs &a, const qmann_net *net, const void *keys, const int8_t *vals, size_t key_hop_stride,
-              size_t val_hop_stride, const uint32_t *row_off, const float *u0, float *u_out, const qmann_taps *taps)
+// what the Hamming family asks of a hop besides (hops_host.h::fill_hop_args): attention word length 7 with an integer bit
+int check_ham_hop(const qmann_net *net, uint32_t h)
 {
-    if (!net || !keys || !vals || !row_off || !u0 || !u_out) return QMANN_EINVAL;
-    if (net->n_hop == 0 || net->n_hop > QMANN_MAX_HOP) return QMANN_EINVAL;
-    if (net->dim_emb == 0 || net->dim_emb > net->dim_emb_pad) return QMANN_EINVAL;
-    if (net->dim_emb_pad != 64 && net->dim_emb_pad != 128 && net->dim_emb_pad != 256) return QMANN_EUNSUPPORTED;
-    if (net->softmax_base > QMANN_SOFTMAX_EXP_PLAN) return QMANN_EINVAL;
-    if (!fmt8(net->bin) && net->bin.iwl + net->bin.frac != 0) return QMANN_ERANGE;     // (0,0) = BINARY_MODE: u binarised
-    for (uint32_t h = 0; h < net->n_hop; h++) {
-        if (!fmt8(net->act[h]) || !fmt8(net->w[h]) || !fmt8(net->att[h])) return QMANN_ERANGE;
-        if (net->att[h].iwl + net->att[h].frac != 7 || net->att[h].iwl < 1) return QMANN_EUNSUPPORTED;
-        if (net->en_lin_map && !net->lin_map[h]) return QMANN_EINVAL;
-    }
-    a = HopArgs{};
+    return (net->att[h].iwl + net->att[h].frac != 7 || net->att[h].iwl < 1) ? QMANN_EUNSUPPORTED : QMANN_OK;
+}
+
+// HopArgs of a Hamming-family call: the shared checks and fields, then what only this family carries
+int fill_ham_args(HopArgs &a, const qmann_net *net, const void *keys, const int8_t *vals, size_t key_hop_stride,
+                  size_t val_hop_stride, const uint32_t *row_off, const float *u0, float *u_out, const qmann_taps *taps)
+{
+    if (const int rc = fill_hop_args(a, net, keys, vals, key_hop_stride, val_hop_stride, row_off, u0, u_out, taps, check_ham_hop)) return rc;
     // Mode 3 does word arithmetic on its operands before it compares bits: a byte per operand carries that only for the grid
     // combinations of qfmt.h::ham_hop_kind.  u entering hop h comes from emb_q (format w[0]) or from sv[h-1] (format act[h-1]);
     // the keys of hop h lie on w[h].  (Modes 10 / 11 compare the words' top bits as they are: any grid.)
     if (net->attention_mode == QMANN_ATT_APPX)
         for (uint32_t h = 0; h < net->n_hop; h++) {
-            const qmann_fmt src = h == 0 ? net->w[0] : net->act[h - 1];
-            const int kind = ham_hop_kind(QFmt{src.iwl, src.frac}, QFmt{net->w[h].iwl, net->w[h].frac}, QFmt{net->att[h].iwl, net->att[h].frac});
+            const int kind = ham_hop_kind(qm_qfmt(h == 0 ? net->w[0] : net->act[h - 1]), a.w[h], a.att[h]);
             if (kind == kHamNone) return QMANN_EUNSUPPORTED;
             a.ham_kinds |= (uint32_t)kind << (2u * h);
         }
-    a.keys = (const int8_t *)keys; a.vals = vals; a.row_off = row_off;
-    a.hop_stride = val_hop_stride; a.key_hop_stride = key_hop_stride;
-    a.u0 = u0; a.u_out = u_out;
-    if (taps) {
-        a.tap_codes = taps->score_codes; a.tap_scores = taps->scores; a.tap_probs = taps->probs;
-        a.tap_o = taps->o; a.tap_u = taps->u;
-    }
-    a.rows_total = val_hop_stride ? (uint32_t)(val_hop_stride / net->dim_emb_pad) : (uint32_t)qm_rows_hint;   // (tied hops: the caller's hint, or 0 = unknown)
-    a.n_hop = net->n_hop; a.D = net->dim_emb; a.Dp = net->dim_emb_pad;
-    a.softmax_base = net->softmax_base; a.en_lin_map = net->en_lin_map;
-    a.softmax_shift = net->softmax_shift_based; a.en_att_scale = net->en_att_scale; a.en_non_lin = net->en_non_linearity;
-    for (uint32_t h = 0; h < net->n_hop; h++) {
-        a.att_scale[h] = net->att_scale[h];
-        a.lin_map[h] = net->lin_map[h];
-        a.act[h] = QFmt{net->act[h].iwl, net->act[h].frac};
-        a.w[h] = QFmt{net->w[h].iwl, net->w[h].frac};
-        a.att[h] = QFmt{net->att[h].iwl, net->att[h].frac};
-    }
-    a.bin = QFmt{net->bin.iwl, net->bin.frac};
     return QMANN_OK;
 }
 
-template <int LPRK, int DP, int MODE, int NB>
-void launch(const HopArgs &a, uint32_t key_row_bytes, size_t lds, uint32_t lds_slots, uint32_t n_query, hipStream_t st)
+// lean / small (hops_host.h::launch_hops) for one attention mode of the family, k_hops_ham for memories beyond 64 slots
+template <int MODE, int NB, int DP, int LPRK>
+void launch_ham(const HopArgs &a, size_t lds, uint32_t max_slots, uint32_t n_query, hipStream_t st)
 {
-    if (lds > kLdsDefaultLimit)
-        QM_HIP(hipFuncSetAttribute((const void *)k_hops_ham<LPRK, DP, MODE, NB>,
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    k_hops_ham<LPRK, DP, MODE, NB><<<n_query, kBlock, lds, st>>>(a, key_row_bytes, lds_slots);
+    launch_hops<MODE, NB, DP / 16, LPRK>(a, max_slots, n_query, st, [&] {
+        qm_launch(k_hops_ham<LPRK, DP, MODE, NB>, n_query, kBlock, lds, st, a, 16u * LPRK, max_slots);
+    });
 }
 
 size_t ham_lds_bytes(uint32_t max_slots, uint32_t v0_bins)
@@ -365,29 +339,20 @@ int qmann_hops_appx_impl(const qmann_net *net, const int8_t *keys, const int8_t 
 {
     QmBatched qm_scope;
     HopArgs a;
-    const int rc = fill_args(a, net, keys, vals, hop_stride, hop_stride, row_off, u0, u_out, taps);
-    if (rc) return rc;
+    if (const int rc = fill_ham_args(a, net, keys, vals, hop_stride, hop_stride, row_off, u0, u_out, taps)) return rc;
     a.max_slots = max_slots;
     const size_t lds = ham_lds_bytes(max_slots, 0);
     if (lds > 160 * 1024 - 1024) return QMANN_ERANGE;
     if (n_query == 0) return QMANN_OK;
-    if (n_query >= (1u << 24)) return QMANN_ERANGE;      // one workgroup per query: a launch holds < 2^32 threads
+    if (qm_too_many_queries(n_query)) return QMANN_ERANGE;
     hipStream_t st = (hipStream_t)stream;
     const bool mq = a.ham_kinds != 0;                       // some hop's operands leave the attention grid (EN_MQ): the kernels
                                                             // that carry all three lane sums (ham_common.h)
-#define QM_APPX(M)                                                                                                    \
-    do {                                                                                                              \
-        if (lean_supported(a, max_slots, 64)) launch_lean<M, 8>(a, max_slots, n_query, st);       /* hops_lean.h */   \
-        else if (max_slots <= (uint32_t)kWave) {                                                  /* hops_small.h */  \
-            if (net->dim_emb_pad == 64) k_hops_small<4, 4, M, 8><<<n_query, kWave, 0, st>>>(a, 64);                   \
-            else if (net->dim_emb_pad == 128) k_hops_small<8, 8, M, 8><<<n_query, kWave, 0, st>>>(a, 128);            \
-            else k_hops_small<16, 16, M, 8><<<n_query, kWave, 0, st>>>(a, 256);                                       \
-        } else if (net->dim_emb_pad == 64) launch<4, 64, M, 8>(a, 64, lds, max_slots, n_query, st);                   \
-        else if (net->dim_emb_pad == 128) launch<8, 128, M, 8>(a, 128, lds, max_slots, n_query, st);                  \
-        else launch<16, 256, M, 8>(a, 256, lds, max_slots, n_query, st);                                              \
-    } while (0)
-    if (mq) QM_APPX(kModeAppxMq); else QM_APPX(kModeAppx);
-#undef QM_APPX
+    qm_dispatch<64, 128, 256>(a.Dp, [&](auto dp) {
+        constexpr int DP = decltype(dp)::value;
+        if (mq) launch_ham<kModeAppxMq, 8, DP, DP / 16>(a, lds, max_slots, n_query, st);
+        else launch_ham<kModeAppx, 8, DP, DP / 16>(a, lds, max_slots, n_query, st);
+    });
     QM_LAUNCH_CHECK();
     return qm_scope.rc();
 }
@@ -401,37 +366,21 @@ int qmann_hops_hambytes_impl(const qmann_net *net, const int8_t *keys, const int
     const uint32_t nb = net->num_bit, Dp = net->dim_emb_pad;
     if (nb != 1 && nb != 2 && nb != 4 && nb != 8) return QMANN_EUNSUPPORTED;
     HopArgs a;
-    const int rc = fill_args(a, net, keys, vals, hop_stride, hop_stride, row_off, u0, u_out, taps);
-    if (rc) return rc;
+    if (const int rc = fill_ham_args(a, net, keys, vals, hop_stride, hop_stride, row_off, u0, u_out, taps)) return rc;
     a.max_slots = max_slots;
     const bool v1 = net->attention_mode == QMANN_ATT_HAMMING_V1;
     const size_t lds = ham_lds_bytes(max_slots, v1 ? 0u : nb * net->dim_emb + 1u);
     if (lds > 160 * 1024 - 1024) return QMANN_ERANGE;
     if (n_query == 0) return QMANN_OK;
-    if (n_query >= (1u << 24)) return QMANN_ERANGE;      // one workgroup per query: a launch holds < 2^32 threads
+    if (qm_too_many_queries(n_query)) return QMANN_ERANGE;
     hipStream_t st = (hipStream_t)stream;
-    if (lean_supported(a, max_slots, Dp)) {                 // hops_lean.h
-        if (v1) { if (nb == 1) launch_lean<kModeV1Bytes, 1>(a, max_slots, n_query, st); else if (nb == 2) launch_lean<kModeV1Bytes, 2>(a, max_slots, n_query, st);
-                  else if (nb == 4) launch_lean<kModeV1Bytes, 4>(a, max_slots, n_query, st); else launch_lean<kModeV1Bytes, 8>(a, max_slots, n_query, st); }
-        else { if (nb == 1) launch_lean<kModeV0Bytes, 1>(a, max_slots, n_query, st); else if (nb == 2) launch_lean<kModeV0Bytes, 2>(a, max_slots, n_query, st);
-               else if (nb == 4) launch_lean<kModeV0Bytes, 4>(a, max_slots, n_query, st); else launch_lean<kModeV0Bytes, 8>(a, max_slots, n_query, st); }
-        QM_LAUNCH_CHECK();
-        return qm_scope.rc();
-    }
-#define QM_HAMB(DP, NB)                                                                                   \
-    do {                                                                                                  \
-        constexpr int L = DP / 16;                                                                        \
-        if (max_slots <= (uint32_t)kWave) {                 /* hops_small.h */                            \
-            if (v1) k_hops_small<L, L, kModeV1Bytes, NB><<<n_query, kWave, 0, st>>>(a, DP);               \
-            else k_hops_small<L, L, kModeV0Bytes, NB><<<n_query, kWave, 0, st>>>(a, DP);                  \
-        } else if (v1) launch<L, DP, kModeV1Bytes, NB>(a, DP, lds, max_slots, n_query, st);               \
-        else launch<L, DP, kModeV0Bytes, NB>(a, DP, lds, max_slots, n_query, st);                         \
-    } while (0)
-#define QM_HAMB_NB(DP)                                                                                    \
-    do { if (nb == 1) QM_HAMB(DP, 1); else if (nb == 2) QM_HAMB(DP, 2); else if (nb == 4) QM_HAMB(DP, 4); else QM_HAMB(DP, 8); } while (0)
-    if (Dp == 64) QM_HAMB_NB(64); else if (Dp == 128) QM_HAMB_NB(128); else QM_HAMB_NB(256);
-#undef QM_HAMB_NB
-#undef QM_HAMB
+    qm_dispatch<64, 128, 256>(Dp, [&](auto dp) {
+        qm_dispatch<1, 2, 4, 8>(nb, [&](auto n) {
+            constexpr int DP = decltype(dp)::value, NB = decltype(n)::value;
+            if (v1) launch_ham<kModeV1Bytes, NB, DP, DP / 16>(a, lds, max_slots, n_query, st);
+            else launch_ham<kModeV0Bytes, NB, DP, DP / 16>(a, lds, max_slots, n_query, st);
+        });
+    });
     QM_LAUNCH_CHECK();
     return qm_scope.rc();
 }
@@ -449,30 +398,24 @@ int qmann_hops_packed(const qmann_net *net, const uint64_t *key_planes, size_t k
     if (key_hop_stride != val_hop_stride / Dp * (Dp / 64) * nb * 8) return QMANN_EINVAL;
     if (taps && val_hop_stride == 0) return QMANN_EINVAL;   // taps are indexed [hop][row]: they need distinct hop planes
     HopArgs a;
-    const int rc = fill_args(a, net, key_planes, vals, key_hop_stride, val_hop_stride, row_off, u0, u_out, taps);
-    if (rc) return rc;
+    if (const int rc = fill_ham_args(a, net, key_planes, vals, key_hop_stride, val_hop_stride, row_off, u0, u_out, taps)) return rc;
     a.max_slots = max_slots;
     const bool v1 = net->attention_mode == QMANN_ATT_HAMMING_V1;
     const size_t lds = ham_lds_bytes(max_slots, v1 ? 0u : nb * net->dim_emb + 1u);
     if (lds > 160 * 1024 - 1024) return QMANN_ERANGE;
-    const uint32_t row_bytes = Dp / 64 * nb * 8;
-    if (row_bytes < 16) return QMANN_EUNSUPPORTED;      // Dp = 64 with a single plane
+    if (Dp / 64 * nb * 8 < 16) return QMANN_EUNSUPPORTED;      // Dp = 64 with a single plane: a key row is half a 16-byte load
     if (n_query == 0) return QMANN_OK;
-    if (n_query >= (1u << 24)) return QMANN_ERANGE;      // one workgroup per query: a launch holds < 2^32 threads
+    if (qm_too_many_queries(n_query)) return QMANN_ERANGE;
     hipStream_t st = (hipStream_t)stream;
-#define QM_HAM(DP, NB)                                                                                   \
-    do {                                                                                                 \
-        constexpr int LPRK = (DP / 64) * NB * 8 / 16;                                                    \
-        if (max_slots <= (uint32_t)kWave) {                 /* hops_small.h */                           \
-            if (v1) k_hops_small<DP / 16, LPRK, kModeV1, NB><<<n_query, kWave, 0, st>>>(a, row_bytes);   \
-            else k_hops_small<DP / 16, LPRK, kModeV0, NB><<<n_query, kWave, 0, st>>>(a, row_bytes);      \
-        } else if (v1) launch<LPRK, DP, kModeV1, NB>(a, row_bytes, lds, max_slots, n_query, st);         \
-        else launch<LPRK, DP, kModeV0, NB>(a, row_bytes, lds, max_slots, n_query, st);                   \
-    } while (0)
-    if (Dp == 64) { if (nb == 2) QM_HAM(64, 2); else if (nb == 4) QM_HAM(64, 4); else QM_HAM(64, 8); }
-    else if (Dp == 128) { if (nb == 1) QM_HAM(128, 1); else if (nb == 2) QM_HAM(128, 2); else if (nb == 4) QM_HAM(128, 4); else QM_HAM(128, 8); }
-    else { if (nb == 1) QM_HAM(256, 1); else if (nb == 2) QM_HAM(256, 2); else if (nb == 4) QM_HAM(256, 4); else QM_HAM(256, 8); }
-#undef QM_HAM
+    qm_dispatch<64, 128, 256>(Dp, [&](auto dp) {
+        qm_dispatch<1, 2, 4, 8>(nb, [&](auto n) {
+            constexpr int DP = decltype(dp)::value, NB = decltype(n)::value, LPRK = (DP / 64) * NB * 8 / 16;
+            if constexpr (LPRK >= 1) {                      // (no instantiation for the case refused above)
+                if (v1) launch_ham<kModeV1, NB, DP, LPRK>(a, lds, max_slots, n_query, st);
+                else launch_ham<kModeV0, NB, DP, LPRK>(a, lds, max_slots, n_query, st);
+            }
+        });
+    });
     QM_LAUNCH_CHECK();
     return qm_scope.rc();
 }

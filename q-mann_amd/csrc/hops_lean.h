@@ -596,11 +596,7 @@ inline void launch_lean_w(HopArgs a, uint32_t max_slots, uint32_t n_query, hipSt
     // bound by vector issue: the late workgroups run twice as fast) -- for the latency-bound embedding kernel the same mistake
     // doubled the run time.
     const uint32_t need = (n_query + kLeanWaves - 1) / kLeanWaves;
-    auto go = [&](auto kernel, int wps) {
-        if (lds > kLdsDefaultLimit) QM_HIP(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        const uint32_t resident = qm_resident_groups(kLeanWaves, (unsigned)wps, lds);
-        kernel<<<need < resident ? need : resident, kLeanBlock, lds, st>>>(a, la);
-    };
+    auto go = [&](auto kernel, unsigned wps) { qm_launch_persistent(kernel, need, QmPersistent{kLeanWaves, wps}, lds, st, a, la); };
     // the six-wave build where it buys a third workgroup per CU (every attention mode: the Hamming forms need 81-91 registers in
     // the four-wave build and all but the EN_MQ mode-3 form fit 80 without a spill; 50-slot synthetic memories in an interleaved
     // A/B: mode 3 0.91 -> 0.84 ms, weighted Hamming 0.70 -> 0.65 ms)
@@ -723,8 +719,9 @@ inline void launch_lean_all(const HopArgs &a, uint32_t max_slots, uint32_t n_que
             sparse = true;
     }
     if (qm_tuning().lean_sparse >= 0) sparse = qm_tuning().lean_sparse == 1;
-    if (w7) { if (sparse) launch_lean_w<MODE, NB, true, true>(a, max_slots, n_query, st, list, n_list, n_other); else launch_lean_w<MODE, NB, true, false>(a, max_slots, n_query, st, list, n_list, n_other); }
-    else { if (sparse) launch_lean_w<MODE, NB, false, true>(a, max_slots, n_query, st, list, n_list, n_other); else launch_lean_w<MODE, NB, false, false>(a, max_slots, n_query, st, list, n_list, n_other); }
+    qm_dispatch<false, true>(w7, [&](auto w) {
+        qm_dispatch<false, true>(sparse, [&](auto sp) { launch_lean_w<MODE, NB, decltype(w)::value, decltype(sp)::value>(a, max_slots, n_query, st, list, n_list, n_other); });
+    });
 }
 
 }  // namespace

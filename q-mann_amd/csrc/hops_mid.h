@@ -222,11 +222,8 @@ inline void launch_mid_w(HopArgs a, uint32_t max_slots, uint32_t n_query, hipStr
     la.lm_in_lds = a.en_lin_map ? 1u : 0u;
     a.rows_total = n_query;                                               // (no taps: the field carries the query count)
     const size_t lds = a.n_hop * 1024u + (la.lm_in_lds ? a.n_hop * kLmHopBytes : 0u) + (size_t)kMidWaves * (kLwBytes + la.rows_pad);
-    if (lds > kLdsDefaultLimit)
-        QM_HIP(hipFuncSetAttribute((const void *)k_hops_mid<W7>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const uint32_t need = (n_query + kMidWaves - 1) / kMidWaves;
-    const uint32_t resident = qm_resident_groups(kMidWaves, (2 * kMidWaves + 3) / 4, lds);   // (the kernel's __launch_bounds__)
-    k_hops_mid<W7><<<need < resident ? need : resident, kMidBlock, lds, st>>>(a, la);
+    qm_launch_persistent(k_hops_mid<W7>, need, QmPersistent{kMidWaves, (2 * kMidWaves + 3) / 4}, lds, st, a, la);   // (the kernel's __launch_bounds__)
 }
 
 inline void launch_mid(const HopArgs &a, uint32_t max_slots, uint32_t n_query, hipStream_t st)
@@ -235,8 +232,7 @@ inline void launch_mid(const HopArgs &a, uint32_t max_slots, uint32_t n_query, h
     for (uint32_t h = 0; h < a.n_hop; h++)
         w7 = w7 && a.att[h].iwl + a.att[h].frac == 7 && (!a.en_lin_map || a.w[h].iwl + a.w[h].frac == 7) &&
              a.act[h].iwl + a.act[h].frac == 7;                       // (lean_finish_hop<true> folds every word length to 7)
-    if (w7) launch_mid_w<true>(a, max_slots, n_query, st);
-    else launch_mid_w<false>(a, max_slots, n_query, st);
+    qm_dispatch<false, true>(w7, [&](auto w) { launch_mid_w<decltype(w)::value>(a, max_slots, n_query, st); });
 }
 
 }  // namespace

@@ -499,10 +499,7 @@ inline void launch_quad(HopArgs a, const QuadArgs &qa, uint32_t n_max, hipStream
     const size_t lds = (la.exp_table ? a.n_hop * 1024u : 0u) + (la.lm_in_lds ? a.n_hop * kLmHopBytes : 0u) + (size_t)kQuadWaves * 4u * kQwBytes;
     const uint32_t need = (n_max + kQuadWaves * 4u - 1u) / (kQuadWaves * 4u);
     constexpr int wps = NC == 1 ? kQuadWps : kQuadWpsLong;
-    auto kernel = k_hops_quad<MODE, NB, wps, NC>;
-    if (lds > kLdsDefaultLimit) QM_HIP(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const uint32_t resident = qm_resident_groups(kQuadWaves, (unsigned)wps, lds);
-    kernel<<<need < resident ? need : resident, kQuadBlock, lds, st>>>(a, la, qa);
+    qm_launch_persistent(k_hops_quad<MODE, NB, wps, NC>, need, QmPersistent{kQuadWaves, wps}, lds, st, a, la, qa);
 }
 
 }  // namespace

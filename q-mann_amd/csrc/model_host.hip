@@ -430,7 +430,7 @@ int qmann_model_forward_words(qmann_model *m, const uint16_t *story_words, uint3
     if (rc) return rc;
     // Large batches: the question embedding on a second stream BESIDE the story embedding (forked and joined by events: one ordered
     // step to the caller's stream, both branches to a stream capture).  The story kernels are latency-bound persistent grids that
-    // leave 32 .. 80 registers per SIMD lane unallocated; the question kernel is built to fit 32 (batch_io.hip) and is bound by its
+    // leave 32 .. 80 registers per SIMD lane unallocated; the question kernel is built to fit 32 (batch_embed_idx.hip) and is bound by its
     // own stores, so its workgroups run in that room.  Launched AFTER the story kernel, so that one keeps its full residency.
     QmSide *sd = (n_query >= kQmCorunMinQueries && !qm_tuning().no_corun) ? qm_side_stream((hipStream_t)stream) : nullptr;
     if (sd) {

@@ -9,6 +9,7 @@
 // all products / sums of such values are exact small integers.
 #pragma once
 #include <stdint.h>
+#include "../../include/qmann_batch.h"
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
@@ -24,6 +25,10 @@ struct QFmt {
     uint32_t iwl;
     uint32_t frac;
 };
+
+// the public qmann_fmt (include/qmann_batch.h: the same two fields) as a QFmt, and "this format fits a signed byte"
+static inline QFmt qm_qfmt(qmann_fmt f) { return QFmt{f.iwl, f.frac}; }
+static inline bool qm_fmt8(qmann_fmt f) { return f.iwl + f.frac >= 1 && f.iwl + f.frac <= 7; }
 
 // two's-complement integer code of Q(x)
 QM_HD int32_t qm_code(float x, uint32_t iwl, uint32_t frac)

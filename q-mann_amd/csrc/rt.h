@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <type_traits>
 
 // The batched entry points (qmann_*: they return QMANN_E* codes) do not end the host process on a HIP failure: inside a
 // QmBatched scope the failure is reported on stderr, remembered, and the entry point returns QMANN_EHIP.  The drop-in
@@ -126,3 +127,45 @@ constexpr uint32_t kQmCorunMinQueries = 32768;        // batches below run their
 QmSide *qm_side_stream(hipStream_t stream);       // (tuning.hip)
 
 static inline unsigned qm_cdiv(unsigned a, unsigned b) { return (a + b - 1) / b; }
+
+// The batched entry points give one workgroup (or wavefront) to a query: a launch holds < 2^32 threads
+static inline bool qm_too_many_queries(uint32_t n_query) { return n_query >= (1u << 24); }
+
+// ---- launches -------------------------------------------------------------------------------------------------------------
+// dynamic LDS a kernel may use without hipFuncSetAttribute (static arrays come on top, hence the margin)
+constexpr size_t kLdsDefaultLimit = 48 * 1024;
+
+// One launch: beyond the default limit the kernel's dynamic-LDS limit is raised first (no cached state: thread- and
+// device-safe).  The caller checks the launch (QM_LAUNCH_CHECK).
+template <typename... P, typename... A>
+static inline void qm_launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t stream, const A &...args)
+{
+    if (lds > kLdsDefaultLimit)
+        QM_HIP(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    kernel<<<grid, block, lds, stream>>>(args...);
+}
+
+// A persistent kernel's workgroup: `waves` wavefronts, compiled for `waves_per_simd` (its __launch_bounds__); `static_lds`: LDS
+// the residency rule counts on top of the launch's dynamic bytes; `grid_y`: the residents are shared among this many planes of
+// a two-dimensional grid.
+// (static_lds has one user, k_answer_mfma's 256 bytes, kept as its launcher always had it -- on top of the 256 that
+// qm_resident_groups adds itself, so that margin is counted twice; grid_y has one user, k_embed_story_mfma.  Whether the
+// first should go is a question of grid size, hence of timing: for a change of its own.)
+struct QmPersistent { unsigned waves, waves_per_simd; size_t static_lds = 0; unsigned grid_y = 1; };
+
+// A persistent launch: `need` workgroups' worth of work (per plane), never more workgroups than are resident at once
+// (qm_resident_groups above)
+template <typename... P, typename... A>
+static inline void qm_launch_persistent(void (*kernel)(P...), uint32_t need, QmPersistent wg, size_t lds, hipStream_t stream, const A &...args)
+{
+    const uint32_t resident = qm_resident_groups(wg.waves, wg.waves_per_simd, lds + wg.static_lds);
+    const uint32_t cap = resident / wg.grid_y ? resident / wg.grid_y : 1u;
+    qm_launch(kernel, dim3(need < cap ? need : cap, wg.grid_y), dim3(wg.waves * 64u), lds, stream, args...);
+}
+
+// Run-time value -> template argument: f(std::integral_constant<.., V>{}) for the listed V that equals v; false when none does
+template <auto... Vs, typename T, typename F>
+static inline bool qm_dispatch(T v, F &&f)
+{
+    return ((v == (T)Vs ? (f(std::integral_constant<decltype(Vs), Vs>{}), true) : false) || ...);
+}

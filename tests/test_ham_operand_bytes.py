@@ -18,7 +18,7 @@ def grid_values(fmt):
 
 
 def key_bytes(values, kind, wk, att):
-    """the rule of csrc/batch_io.hip (ew_to_bytes / sm_byte with the minus-zero flag) and of ham_ubyte (csrc/ham_common.h)"""
+    """the rule of csrc/batch_embed_idx.hip::ew_to_bytes / csrc/batch_embed.hip::sm_byte (with the minus-zero flag) and of ham_ubyte (csrc/ham_common.h)"""
     v = values.astype(np.float64)
     if kind == "fine":
         mag = np.minimum(np.floor(np.abs(v) * (1 << wk[1])), 127)
