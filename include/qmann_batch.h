@@ -142,6 +142,21 @@ int qmann_hops_i8(const qmann_net *net, const int8_t *keys, const int8_t *vals, 
                   const uint32_t *row_off, uint32_t max_slots, const float *u0, float *u_out,
                   const qmann_taps *taps, uint32_t n_query, void *stream);
 
+/* qmann_hops_i8 when every query reads the SAME memory: keys, vals int8 [n_hop][n_slots][Dp] sign-magnitude (the layout of
+ * qmann_hops_i8; hop_stride bytes between hop planes, 0 = tied hops), u0 / u_out [n_query][D].  Results are those of
+ * qmann_hops_i8 on n_query copies of the plane, bit for bit.
+ * taps (any pointer may be NULL): score_codes / scores / probs [n_hop][n_query][n_slots], o / u [n_query][n_hop][D]; they are
+ * indexed by query, not by plane row, so they are allowed with hop_stride = 0.
+ * One workgroup owns a tile of 1, 2, 4 or 8 queries and scans the plane once per hop for all of them (the plane stays in L2;
+ * csrc/batch_hops_shared.hip); the library chooses the tile, QMANN_SHARED_QT (environment) forces one that fits.
+ * attention_mode QMANN_ATT_FIXED only -- every qmann_net field qmann_hops_i8 honours in that mode is honoured; any other
+ * attention mode returns QMANN_EUNSUPPORTED with nothing launched (the Hamming and float forms are follow-ups).
+ * n_slots = 0: QMANN_EINVAL.  A memory too long for LDS with one query per workgroup: QMANN_ERANGE (sizing helper below).
+ * One ordered step on `stream`, no second stream, no library scratch: it can be captured in a graph. */
+int qmann_hops_shared_i8(const qmann_net *net, const int8_t *keys, const int8_t *vals, size_t hop_stride,
+                         uint32_t n_slots, const float *u0, float *u_out, const qmann_taps *taps,
+                         uint32_t n_query, void *stream);
+
 /* Packed binary codes for the Hamming forms: sign-magnitude bytes [rows][Dp] -> bit planes
  * uint64 [rows][Dp/64][num_bit] (plane 0 = sign bits, plane i = magnitude bit 7-i; bit b of a word
  * is column 64.g + b).  num_bit in 1..8.  sm_codes 16-byte aligned, planes 8-byte aligned (QMANN_EINVAL otherwise). */
@@ -244,9 +259,15 @@ int qmann_check_slots(const uint32_t *row_off, uint32_t n_query, uint32_t max_sl
 
 /* bytes of LDS one workgroup of qmann_hops_i8 needs for `max_slots` slots (for sizing checks) */
 size_t qmann_hops_lds_bytes(uint32_t max_slots);
+/* ... and one workgroup of qmann_hops_shared_i8 that owns `queries_per_group` queries of an `n_slots`-slot memory; the call
+ * needs this to stay within 160 KiB - 1 KiB for queries_per_group = 1 */
+size_t qmann_hops_shared_lds_bytes(uint32_t n_slots, uint32_t queries_per_group);
+/* queries per workgroup qmann_hops_shared_i8 would take for this call on the current device, QMANN_SHARED_QT included
+ * (1, 2, 4 or 8; 0 where the call would launch nothing) -- for tests and timing tools that must know which tile ran */
+uint32_t qmann_hops_shared_tile(uint32_t n_slots, uint32_t n_query);
 
 /* The library's A/B switches (environment variables QMANN_NO_LEAN, QMANN_NO_MID, QMANN_NO_W7, QMANN_NO_TIED, QMANN_NO_TIGHT,
- * QMANN_LEAN_SPARSE, QMANN_EMBED_VALU, QMANN_EMBED_GENERAL_EPILOGUE, QMANN_ANSWER_TWO_PASS: INTEGRATION.md) are read ONCE,
+ * QMANN_SHARED_QT, QMANN_LEAN_SPARSE, QMANN_EMBED_VALU, QMANN_EMBED_GENERAL_EPILOGUE, QMANN_ANSWER_TWO_PASS: INTEGRATION.md) are read ONCE,
  * at the first call that needs one; no launch touches the environment afterwards.  A host that changes one later calls
  * this to have them read again -- from one thread, while no other thread is inside the library. */
 void qmann_tuning_reload(void);

@@ -91,6 +91,15 @@ int qmann_model_forward_words(qmann_model *m, const uint16_t *story_words, uint3
                               uint32_t max_slots, uint32_t n_query, const uint32_t *answer, uint32_t *pred,
                               float *cost, uint32_t *match, void *stream);
 
+/* One story, many questions: story_words [n_rows][max_words] is embedded ONCE (every hop, or one plane when the hops are tied)
+ * and all n_query questions attend to it.  Same results as qmann_model_forward_words on n_query copies of the story.
+ * The workspace holds n_rows rows of memory, not n_query x n_rows.  Attention mode QMANN_ATT_FIXED only (what
+ * qmann_hops_shared_i8 covers): any other model returns QMANN_EUNSUPPORTED; n_rows = 0 returns QMANN_EINVAL.  answer, pred,
+ * cost, match as above; qmann_model_last_u holds the final state afterwards.  All work goes to `stream` itself. */
+int qmann_model_forward_shared_words(qmann_model *m, const uint16_t *story_words, uint32_t n_rows, uint32_t max_words,
+                                     const uint16_t *question_words, uint32_t max_q_words, uint32_t n_query,
+                                     const uint32_t *answer, uint32_t *pred, float *cost, uint32_t *match, void *stream);
+
 /* Forward from the reference's float bag-of-words pools (dev_m_test / dev_q_test, MemN2N.c:2337-2349):
  *   story [rows_total][dim_input] float, question [n_query][dim_input] float. */
 int qmann_model_forward_bow(qmann_model *m, const float *story, uint32_t rows_total, const float *question,

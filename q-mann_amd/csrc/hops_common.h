@@ -448,6 +448,72 @@ __device__ __forceinline__ double block_serial_total_f32(uint32_t S, uint32_t la
     return r;
 }
 
+// (A COPY of the stage k_hops_fixed carries inline, batch_hops.hip -- calling this from there changes that kernel's device
+// assembly (tools/device_asm_equal.sh), so the move is left to a change that re-measures the headline; keep the two in step.)
+// Softmax over the slots of one query from the per-wavefront histograms of its score codes (bin d <-> code d - 127), the
+// per-slot taps (written from index `tap_base` on), and the list of rows whose quantised weight is non-zero.  `hist` .. `red`:
+// the query's pieces of the LDS carve-up above; S > 0 score bytes in `sc`.  Called by the whole workgroup (nthreads threads,
+// nwaves wavefronts) after a barrier behind the scan; ends with a barrier.  Returns the number of surviving rows.
+__device__ __forceinline__ uint32_t hist_softmax_survivors(const HopArgs &a, uint32_t h, uint32_t S, size_t tap_base, uint32_t *hist,
+                                                           float *ptab, uint8_t *kplut, const int8_t *sc, uint32_t *live_row,
+                                                           uint8_t *live_kp, uint32_t *misc, double *red, uint32_t tid, uint32_t lane,
+                                                           uint32_t wave, uint32_t nthreads, uint32_t nwaves)
+{
+    const QFmt fa = a.act[h], fm = a.att[h];
+    // each thread owns bins tid, tid + nthreads, ... (4 bins per thread in a one-wavefront group)
+    const SmCfg smc = sm_cfg(a, h);
+    auto bin_x = [&](uint32_t d) { return sm_scaled(qm_scale_down((float)((int)d - 127), fm.frac), smc); };
+    float xmax = -INFINITY;
+    for (uint32_t d = tid; d < 256; d += nthreads) {
+        uint32_t cnt = 0;
+        for (uint32_t i = 0; i < nwaves; i++) cnt += hist[i * 256 + d];
+        hist[d] = cnt;                                  // bins are thread-private from here on
+        if (cnt) xmax = fmaxf(xmax, bin_x(d));
+    }
+    xmax = block_max<float>(xmax, (float *)red, lane, wave);
+    double part = 0.0;
+    for (uint32_t d = tid; d < 256; d += nthreads) {
+        const float e = sm_exp(bin_x(d) - xmax, smc);  // score - max: exact on the score grid
+        ptab[d] = e;
+        if (hist[d]) part += (double)hist[d] * (double)e;
+    }
+    // e^x base: the CUDA kernel's double total; the CPU bases: the CPU softmax's float total, slot by slot (above)
+    const double total = smc.base == QMANN_SOFTMAX_EXP ? block_sum_double(part, red, lane, wave)
+                                                       : block_serial_total_f32(S, lane, wave, red, [&](uint32_t r) { return ptab[(int)sc[r] + 127]; });
+    for (uint32_t d = tid; d < 256; d += nthreads) {
+        const float p = hist[d] ? sm_quot(ptab[d], total, smc) : 0.0f;
+        ptab[d] = p;
+        kplut[d] = (uint8_t)qm_code(p, fa.iwl, fa.frac);
+    }
+    __syncthreads();
+
+    if (a.tap_codes || a.tap_scores || a.tap_probs) {
+        for (uint32_t r = tid; r < S; r += nthreads) {
+            const int code = sc[r];
+            if (a.tap_codes) a.tap_codes[tap_base + r] = code;
+            if (a.tap_scores) a.tap_scores[tap_base + r] = qm_scale_down((float)code, fm.frac);
+            if (a.tap_probs) a.tap_probs[tap_base + r] = ptab[code + 127];
+        }
+    }
+    // rows whose quantised weight is non-zero: 16 score bytes per LDS read and their 16 table look-ups in flight
+    // together (one score -> look-up -> branch chain per row left every row two LDS latencies long)
+    for (uint32_t rb = tid * 16; rb < S; rb += nthreads * 16) {
+        const i32x4 v = *(const i32x4 *)(sc + rb);           // (the score array is padded to 16 rows)
+        uint8_t kp[16];
+#pragma unroll
+        for (int i = 0; i < 16; i++) kp[i] = kplut[(int)(int8_t)((uint32_t)v[i / 4] >> (8 * (i % 4))) + 127];
+#pragma unroll
+        for (int i = 0; i < 16; i++) {
+            if (rb + i < S && kp[i]) {
+                const uint32_t n = atomicAdd(&misc[0], 1u);
+                if (n < (uint32_t)kLiveCap) { live_row[n] = rb + i; live_kp[n] = kp[i]; }
+            }
+        }
+    }
+    __syncthreads();
+    return misc[0];
+}
+
 // Stages after the softmax, shared by every attention mode:
 //   read-out  o[c] = Qa( sum_r Qa( Qa(p[r]) . Qa(C[r][c]) ) )   (lib/layer_cuda.cu:547-635 via :2430/:2512)
 //             over the rows whose weight code Q(p) is non-zero (the others contribute exact zeros),

@@ -153,6 +153,18 @@ __device__ __forceinline__ int lane_sum_w(const i32x4 x, const ScanConst &c, uin
 {
     return W7 ? lane_row_sum7(x, c) : lane_row_sum(x, c, sh);
 }
+// The part of lane_row_sum / dword_sum7 that depends on the key alone: 16 sign-magnitude key bytes -> the even / odd magnitudes
+// and the sign bits lane_sum_split takes.  (batch_hops_shared.hip: done once for a tile of queries that scan the same plane.)
+__device__ __forceinline__ void split_key_row(const i32x4 x, i32x4 &ev, i32x4 &od, i32x4 &sn)
+{
+#pragma unroll
+    for (int d = 0; d < 4; d++) {
+        const uint32_t w = (uint32_t)x[d];
+        ev[d] = (int)(w & 0x007F007Fu);
+        od[d] = (int)((w >> 8) & 0x007F007Fu);
+        sn[d] = (int)(w & 0x80808080u);
+    }
+}
 // the same on a row that is already split into even / odd magnitudes and sign bits (the linear maps in LDS)
 template <bool W7>
 __device__ __forceinline__ int lane_sum_split(const i32x4 ev, const i32x4 od, const i32x4 sn, const ScanConst &c, uint32_t sh)

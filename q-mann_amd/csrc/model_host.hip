@@ -455,6 +455,31 @@ int qmann_model_forward_words(qmann_model *m, const uint16_t *story_words, uint3
     return rc ? rc : qm_scope.rc();
 }
 
+int qmann_model_forward_shared_words(qmann_model *m, const uint16_t *story_words, uint32_t n_rows, uint32_t max_words,
+                                     const uint16_t *question_words, uint32_t max_q_words, uint32_t n_query,
+                                     const uint32_t *answer, uint32_t *pred, float *cost, uint32_t *match, void *stream)
+{
+    QmBatched qm_scope;
+    if (!m) return QMANN_EINVAL;
+    if (n_query == 0) return QMANN_OK;
+    if (!story_words || !question_words || !pred) return QMANN_EINVAL;
+    if (m->net.attention_mode != QMANN_ATT_FIXED) return QMANN_EUNSUPPORTED;     // (what qmann_hops_shared_i8 covers)
+    if (n_rows == 0) return QMANN_EINVAL;
+    DeviceScope on(m->device);
+    int rc = ensure(m, n_rows, n_query, false);             // ONE memory of n_rows rows, whatever the number of questions
+    if (rc) return rc;
+    // everything on the caller's stream: the one story is a few rows, there is nothing to run beside it
+    const size_t plane = (size_t)n_rows * m->Dp;
+    rc = qmann_embed_story_idx(&m->emb_net, story_words, n_rows, max_words, 1, m->t_a, m->t_c, m->keys, m->vals, plane, stream);
+    if (rc) return rc;
+    rc = qmann_embed_query_idx(&m->net, question_words, max_q_words, m->t_q, m->u0, n_query, stream);
+    if (rc) return rc;
+    rc = qmann_hops_shared_i8(&m->net, m->keys, m->vals, m->tied ? 0 : plane, n_rows, m->u0, m->u, nullptr, n_query, stream);
+    if (rc) return rc;
+    rc = qmann_answer_f32(&m->net, m->w_ans, m->u, answer, pred, nullptr, cost, match, n_query, stream);
+    return rc ? rc : qm_scope.rc();
+}
+
 int qmann_model_forward_bow(qmann_model *m, const float *story, uint32_t rows_total, const float *question,
                             const uint32_t *row_off, uint32_t max_slots, uint32_t n_query, const uint32_t *answer,
                             uint32_t *pred, float *cost, uint32_t *match, void *stream)

@@ -31,6 +31,11 @@ void read_env(QmTuning &t)
         const char *e = getenv("QMANN_QUAD_MIN_QUERIES");
         t.quad_min_queries = (e && *e) ? (uint32_t)strtoul(e, nullptr, 10) : 8192u;
     }
+    {
+        const char *e = getenv("QMANN_SHARED_QT");
+        const unsigned long v = (e && *e) ? strtoul(e, nullptr, 10) : 0ul;
+        t.shared_qt = (v == 1 || v == 2 || v == 4 || v == 8) ? (uint32_t)v : 0u;     // (anything else: the launcher chooses)
+    }
     t.no_tight = on("QMANN_NO_TIGHT");              // presence-only, like its siblings
 }
 

@@ -261,6 +261,30 @@ class QNet:
                                         self._s()), "qmann_hops_i8")
         return (u_out, tobj) if taps else u_out
 
+    def hops_shared(self, keys, vals, n_slots, u0, taps=False, u_out=None):
+        """qmann_hops_shared_i8: ONE memory for every query.  keys/vals int8 [H][n_slots][Dp], or [1][n_slots][Dp] for tied
+        hops (hop stride 0); u0 [B][D] float.  taps: score_codes / scores / probs [H][B][n_slots], o / u [B][H][D]."""
+        B = u0.shape[0]
+        assert keys.shape in ((self.H, n_slots, self.Dp), (1, n_slots, self.Dp)) and vals.shape == keys.shape
+        assert keys.is_contiguous() and vals.is_contiguous()
+        if u_out is None:
+            u_out = torch.empty_like(u0)
+        tp, tobj = None, None
+        if taps:
+            tobj = HopTaps(
+                torch.zeros((self.H, B, n_slots), dtype=torch.int32, device=self.dev),
+                torch.zeros((self.H, B, n_slots), dtype=torch.float32, device=self.dev),
+                torch.zeros((self.H, B, n_slots), dtype=torch.float32, device=self.dev),
+                torch.zeros((B, self.H, self.D), dtype=torch.float32, device=self.dev),
+                torch.zeros((B, self.H, self.D), dtype=torch.float32, device=self.dev))
+            tp = abi.Taps(tobj.score_codes.data_ptr(), tobj.scores.data_ptr(), tobj.probs.data_ptr(),
+                          tobj.o.data_ptr(), tobj.u.data_ptr())
+        hop_stride = n_slots * self.Dp if keys.shape[0] == self.H else 0          # one plane for several hops: tied
+        abi.check(abi.lib.qmann_hops_shared_i8(C.byref(self.net), _ptr(keys), _ptr(vals), hop_stride, n_slots, _ptr(u0),
+                                               _ptr(u_out), C.byref(tp) if tp else None, B, self._s()),
+                  "qmann_hops_shared_i8")
+        return (u_out, tobj) if taps else u_out
+
     def pack_planes(self, sm_codes: torch.Tensor, num_bit: int) -> torch.Tensor:
         """sign-magnitude int8 [..., rows, Dp] -> packed bit planes int64 [..., rows, Dp/64, num_bit]."""
         assert sm_codes.dtype == torch.int8 and sm_codes.is_contiguous() and sm_codes.shape[-1] == self.Dp
@@ -403,6 +427,16 @@ class HostModel:
                                                     _ptr(question_words), question_words.shape[1], _ptr(row_off),
                                                     max_slots, B, _ptr(answer), _ptr(pred), _ptr(cost), _ptr(match),
                                                     self._s()), "qmann_model_forward_words")
+        return pred, cost, match
+
+    def forward_shared_words(self, story_words, question_words, answer=None):
+        """qmann_model_forward_shared_words: one story [n_rows][W], every question of question_words [B][Wq] attends to it"""
+        B = question_words.shape[0]
+        pred, cost, match = self._out(B, answer)
+        abi.check(abi.lib.qmann_model_forward_shared_words(self.h, _ptr(story_words), story_words.shape[0], story_words.shape[1],
+                                                           _ptr(question_words), question_words.shape[1], B, _ptr(answer),
+                                                           _ptr(pred), _ptr(cost), _ptr(match), self._s()),
+                  "qmann_model_forward_shared_words")
         return pred, cost, match
 
     def forward_bow(self, story, question, row_off, max_slots, answer=None):
