@@ -278,6 +278,7 @@ bool model_for(const Sig &s)
     if (!ok) { (void)hipGetLastError(); return false; }
     const int rc = qmann_model_create_on(&g_model, -1, &net, &w, nullptr);
     if (rc != QMANN_OK) g_model = nullptr;
+    qm_model_answer_exact(g_model, true);             // the queue promises the verb-by-verb loop's results: serial-order float sums
     g_stats.models_built += g_model ? 1 : 0;
     g_stats.ms_model += now_ms() - t0;
     // QMANN_SAVE_WEIGHTS_DIR: the matrices the host program is testing with, in the reference's (disabled) weight-file layout
@@ -368,7 +369,6 @@ bool run_batched(const std::vector<Op> &ops, const Sig &s, const std::vector<Que
     ok = ok && hipMemcpy(&irregular, g_scr.counters, 4, hipMemcpyDeviceToHost) == hipSuccess;      // (also waits for the row_off copy)
     if (!ok) { (void)hipGetLastError(); return false; }
     if (irregular) return false;
-    QmAnswerExact exact_answer_layer;                 // the queue promises the verb-by-verb loop's results: serial-order float sums
     const int rc = qmann_model_forward_bow(g_model, qs[a].m, ro[n], qs[a].q, g_scr.row_off, max_slots, (uint32_t)n, g_scr.label, g_scr.pred,
                                            cost, cnt, nullptr);
     if (rc != QMANN_OK) {

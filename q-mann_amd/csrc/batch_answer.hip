@@ -761,8 +761,8 @@ static int answer_f32_impl(const qmann_net *net, const float *w_ans, const float
     if (qm_too_many_queries(n_query)) return QMANN_ERANGE;
     hipStream_t st = (hipStream_t)stream;
     // bAbI shapes (D <= 64, V <= 256), the e^x and 2^x bases: the fused form on the bf16 matrix cores (k_answer_mfma), within
-    // 1e-5 on the softmax; qmann_answer_exact_scope / QMANN_ANSWER_EXACT keep the serial-order kernels below
-    if (allow_fused && D <= 64u && V <= 256u && net->softmax_base != QMANN_SOFTMAX_EXP_PLAN && !qm_tuning().answer_exact && qm_answer_exact_depth == 0) {
+    // 1e-5 on the softmax; qmann_answer_f32_serial / QMANN_ANSWER_EXACT keep the serial-order kernels below
+    if (allow_fused && D <= 64u && V <= 256u && net->softmax_base != QMANN_SOFTMAX_EXP_PLAN && !qm_tuning().answer_exact) {
         const uint32_t tiles = (V + 15u) / 16u;
         const uint32_t n_task = (n_query + 15u) / 16u, need = (n_task + kAmWaves - 1) / kAmWaves;
         // the smallest listed tile count that holds the dictionary

@@ -193,12 +193,17 @@ __global__ void k_check_slots(const uint32_t *__restrict__ row_off, uint32_t n_q
 
 }  // namespace
 
-// rt.h::QmSplitReady: the launch rule of hops_lean.h::launch_lean for "this batch will be split" (stories capped between 17 and 64
-// rows whose mean length is within the short form's 16), and the two lists computed ahead of the launch
-bool qm_split_applies(size_t rows_total, uint32_t n_query, uint32_t max_slots)
+// rt.h: the plan of the qm_hops_i8 call that the host model is about to make (int8 keys: a key row is Dp bytes; no taps), asked
+// of hops_host.h::hop_plan itself -- with the checks that would end that call before its launch
+bool qm_hops_will_split(const qmann_net *net, size_t plane_rows, uint32_t max_slots, uint32_t n_query)
 {
-    return n_query && max_slots > (uint32_t)kQuadSlots && max_slots <= (uint32_t)kWave && rows_total / n_query <= (size_t)kQuadSlots &&
-           !qm_tuning().no_quad && !qm_tuning().no_lean;
+    const bool fixed = net->attention_mode == QMANN_ATT_FIXED;
+    if (!fixed && net->attention_mode != QMANN_ATT_APPX && net->attention_mode != QMANN_ATT_HAMMING_V0 && net->attention_mode != QMANN_ATT_HAMMING_V1)
+        return false;                                       // (float attention has its own kernels: batch_hops_float.hip)
+    HopArgs a;
+    if (n_query == 0 || qm_too_many_queries(n_query) || fill_hop_formats(a, net)) return false;
+    a.rows_total = (uint32_t)plane_rows;
+    return hop_plan(a, fixed ? (int)kModeFixed : (int)kModeAppx, net->dim_emb_pad, max_slots, n_query).form == HopForm::Split;   // (the byte forms of the Hamming family plan alike)
 }
 
 uint32_t *qm_split_early(const uint32_t *row_off, uint32_t n_query, uint32_t max_slots, hipStream_t owner, hipStream_t run_on)
@@ -207,16 +212,6 @@ uint32_t *qm_split_early(const uint32_t *row_off, uint32_t n_query, uint32_t max
 }
 
 extern "C" {
-
-int qmann_hops_appx_impl(const qmann_net *net, const int8_t *keys, const int8_t *vals, size_t hop_stride,
-                         const uint32_t *row_off, uint32_t max_slots, const float *u0, float *u_out,
-                         const qmann_taps *taps, uint32_t n_query, void *stream);   // batch_hops_ham.hip
-
-int qmann_hops_hambytes_impl(const qmann_net *net, const int8_t *keys, const int8_t *vals, size_t hop_stride,
-                             const uint32_t *row_off, uint32_t max_slots, const float *u0, float *u_out,
-                             const qmann_taps *taps, uint32_t n_query, void *stream);   // batch_hops_ham.hip
-
-int qmann_hops_float_impl(const HopArgs &a, uint32_t Dp, uint32_t max_slots, uint32_t n_query, void *stream);  // batch_hops_float.hip
 
 int qmann_check_slots(const uint32_t *row_off, uint32_t n_query, uint32_t max_slots, uint32_t *n_over, void *stream)
 {
@@ -250,20 +245,21 @@ int qmann_quantize_i8(const float *src, int8_t *dst, size_t rows, uint32_t cols,
     return qm_scope.rc();
 }
 
-int qmann_hops_i8(const qmann_net *net, const int8_t *keys, const int8_t *vals, size_t hop_stride,
-                  const uint32_t *row_off, uint32_t max_slots, const float *u0, float *u_out,
-                  const qmann_taps *taps, uint32_t n_query, void *stream)
+}  // extern "C"
+
+int qm_hops_i8(const qmann_net *net, const int8_t *keys, const int8_t *vals, size_t hop_stride, const uint32_t *row_off, uint32_t max_slots,
+               const float *u0, float *u_out, const qmann_taps *taps, uint32_t n_query, void *stream, const QmHopHints &hints)
 {
     QmBatched qm_scope;
     if (const int rc = check_hop_call(net, keys, vals, row_off, u0, u_out)) return rc;
     if (taps && hop_stride == 0) return QMANN_EINVAL;       // taps are indexed [hop][row]: they need distinct hop planes
     if (net->attention_mode == QMANN_ATT_APPX)
-        return qmann_hops_appx_impl(net, keys, vals, hop_stride, row_off, max_slots, u0, u_out, taps, n_query, stream);
+        return qmann_hops_appx_impl(net, keys, vals, hop_stride, row_off, max_slots, u0, u_out, taps, n_query, stream, hints);
     if (net->attention_mode == QMANN_ATT_HAMMING_V0 || net->attention_mode == QMANN_ATT_HAMMING_V1)
-        return qmann_hops_hambytes_impl(net, keys, vals, hop_stride, row_off, max_slots, u0, u_out, taps, n_query, stream);
+        return qmann_hops_hambytes_impl(net, keys, vals, hop_stride, row_off, max_slots, u0, u_out, taps, n_query, stream, hints);
     if (net->attention_mode != QMANN_ATT_FIXED && net->attention_mode != QMANN_ATT_FLOAT) return QMANN_EUNSUPPORTED;
     HopArgs a;
-    if (const int rc = fill_hop_args(a, net, keys, vals, hop_stride, hop_stride, row_off, u0, u_out, taps)) return rc;
+    if (const int rc = fill_hop_args(a, net, keys, vals, hop_stride, hop_stride, row_off, u0, u_out, taps, hints.plane_rows)) return rc;
     a.max_slots = max_slots;
     const size_t lds = qmann_hops_lds_bytes(max_slots);
     if (lds > 160 * 1024 - 1024) return QMANN_ERANGE;   // a little static LDS is used besides
@@ -274,12 +270,11 @@ int qmann_hops_i8(const qmann_net *net, const int8_t *keys, const int8_t *vals, 
         return qmann_hops_float_impl(a, net->dim_emb_pad, max_slots, n_query, stream);
 
     hipStream_t st = (hipStream_t)stream;
-    bool w7 = !qm_tuning().no_w7;
-    for (uint32_t h = 0; h < net->n_hop; h++) w7 = w7 && net->att[h].iwl + net->att[h].frac == 7;
+    const bool w7 = !qm_tuning().no_w7 && all_w7(a, kW7Att);
     qm_dispatch<4, 8, 16>(net->dim_emb_pad / 16, [&](auto lpr) {
         constexpr int LPR = decltype(lpr)::value;
-        launch_hops<kModeFixed, 8, LPR, LPR>(a, max_slots, n_query, st, [&] {
-            if (mid_supported(a, max_slots)) { launch_mid(a, max_slots, n_query, st); return; }      // hops_mid.h: 65 .. 1 024 slots at bAbI width
+        launch_hops<kModeFixed, 8, LPR, LPR>(a, max_slots, n_query, st, hints, [&](HopForm form) {
+            if (form == HopForm::Mid) { launch_mid(a, max_slots, n_query, st); return; }      // hops_mid.h: 65 .. 1 024 slots at bAbI width
             // memories of 65..256 slots run one wavefront per query with the histogram softmax: four times
             // as many queries resident per CU and no cross-wavefront barriers
             const dim3 block(max_slots <= 256 ? kWave : kBlock);
@@ -291,4 +286,8 @@ int qmann_hops_i8(const qmann_net *net, const int8_t *keys, const int8_t *vals, 
     return qm_scope.rc();
 }
 
-}  // extern "C"
+extern "C" int qmann_hops_i8(const qmann_net *net, const int8_t *keys, const int8_t *vals, size_t hop_stride, const uint32_t *row_off,
+                             uint32_t max_slots, const float *u0, float *u_out, const qmann_taps *taps, uint32_t n_query, void *stream)
+{
+    return qm_hops_i8(net, keys, vals, hop_stride, row_off, max_slots, u0, u_out, taps, n_query, stream, QmHopHints{});
+}

@@ -281,11 +281,20 @@ int check_ham_hop(const qmann_net *net, uint32_t h)
     return (net->att[h].iwl + net->att[h].frac != 7 || net->att[h].iwl < 1) ? QMANN_EUNSUPPORTED : QMANN_OK;
 }
 
-// HopArgs of a Hamming-family call: the shared checks and fields, then what only this family carries
-int fill_ham_args(HopArgs &a, const qmann_net *net, const void *keys, const int8_t *vals, size_t key_hop_stride,
-                  size_t val_hop_stride, const uint32_t *row_off, const float *u0, float *u_out, const qmann_taps *taps)
+size_t ham_lds_bytes(uint32_t max_slots, uint32_t v0_bins)
 {
-    if (const int rc = fill_hop_args(a, net, keys, vals, key_hop_stride, val_hop_stride, row_off, u0, u_out, taps, check_ham_hop)) return rc;
+    return (size_t)kOffScores + (((size_t)max_slots * 2 + 15) & ~(size_t)15) + (v0_bins ? v0_table_bytes(v0_bins) : 0);
+}
+
+// What every entry point of the family does between its own checks and its launch: HopArgs (the shared checks and fields, then
+// what only this family carries), the LDS of k_hops_ham, the batch size.  kHamGo: launch; anything else is the entry point's
+// return code (QMANN_OK for an empty batch).  `late_rc`: an error of the entry point's own that ranks behind the LDS bound.
+constexpr int kHamGo = 1;
+int ham_prepare(HopArgs &a, size_t &lds, const qmann_net *net, const void *keys, const int8_t *vals, size_t key_hop_stride,
+                size_t val_hop_stride, const uint32_t *row_off, uint32_t max_slots, const float *u0, float *u_out,
+                const qmann_taps *taps, uint32_t n_query, const QmHopHints &hints, int late_rc = QMANN_OK)
+{
+    if (const int rc = fill_hop_args(a, net, keys, vals, key_hop_stride, val_hop_stride, row_off, u0, u_out, taps, hints.plane_rows, check_ham_hop)) return rc;
     // Mode 3 does word arithmetic on its operands before it compares bits: a byte per operand carries that only for the grid
     // combinations of qfmt.h::ham_hop_kind.  u entering hop h comes from emb_q (format w[0]) or from sv[h-1] (format act[h-1]);
     // the keys of hop h lie on w[h].  (Modes 10 / 11 compare the words' top bits as they are: any grid.)
@@ -295,21 +304,23 @@ int fill_ham_args(HopArgs &a, const qmann_net *net, const void *keys, const int8
             if (kind == kHamNone) return QMANN_EUNSUPPORTED;
             a.ham_kinds |= (uint32_t)kind << (2u * h);
         }
-    return QMANN_OK;
+    a.max_slots = max_slots;
+    const bool v0 = net->attention_mode == QMANN_ATT_HAMMING_V0;       // (the only mode with a table of bins)
+    lds = ham_lds_bytes(max_slots, v0 ? net->num_bit * net->dim_emb + 1u : 0u);
+    if (lds > 160 * 1024 - 1024) return QMANN_ERANGE;
+    if (late_rc) return late_rc;
+    if (n_query == 0) return QMANN_OK;
+    if (qm_too_many_queries(n_query)) return QMANN_ERANGE;
+    return kHamGo;
 }
 
 // lean / small (hops_host.h::launch_hops) for one attention mode of the family, k_hops_ham for memories beyond 64 slots
 template <int MODE, int NB, int DP, int LPRK>
-void launch_ham(const HopArgs &a, size_t lds, uint32_t max_slots, uint32_t n_query, hipStream_t st)
+void launch_ham(const HopArgs &a, size_t lds, uint32_t max_slots, uint32_t n_query, hipStream_t st, const QmHopHints &hints)
 {
-    launch_hops<MODE, NB, DP / 16, LPRK>(a, max_slots, n_query, st, [&] {
+    launch_hops<MODE, NB, DP / 16, LPRK>(a, max_slots, n_query, st, hints, [&](HopForm) {
         qm_launch(k_hops_ham<LPRK, DP, MODE, NB>, n_query, kBlock, lds, st, a, 16u * LPRK, max_slots);
     });
-}
-
-size_t ham_lds_bytes(uint32_t max_slots, uint32_t v0_bins)
-{
-    return (size_t)kOffScores + (((size_t)max_slots * 2 + 15) & ~(size_t)15) + (v0_bins ? v0_table_bytes(v0_bins) : 0);
 }
 
 }  // namespace
@@ -332,62 +343,53 @@ int qmann_pack_bitplanes(const int8_t *sm_codes, uint64_t *planes, size_t rows, 
     return qm_scope.rc();
 }
 
-// APPX on sign-magnitude int8 keys (called from qmann_hops_i8)
-int qmann_hops_appx_impl(const qmann_net *net, const int8_t *keys, const int8_t *vals, size_t hop_stride,
-                         const uint32_t *row_off, uint32_t max_slots, const float *u0, float *u_out,
-                         const qmann_taps *taps, uint32_t n_query, void *stream)
+// APPX on sign-magnitude int8 keys (called from qm_hops_i8)
+int qmann_hops_appx_impl(const qmann_net *net, const int8_t *keys, const int8_t *vals, size_t hop_stride, const uint32_t *row_off, uint32_t max_slots,
+                         const float *u0, float *u_out, const qmann_taps *taps, uint32_t n_query, void *stream, const QmHopHints &hints)
 {
     QmBatched qm_scope;
     HopArgs a;
-    if (const int rc = fill_ham_args(a, net, keys, vals, hop_stride, hop_stride, row_off, u0, u_out, taps)) return rc;
-    a.max_slots = max_slots;
-    const size_t lds = ham_lds_bytes(max_slots, 0);
-    if (lds > 160 * 1024 - 1024) return QMANN_ERANGE;
-    if (n_query == 0) return QMANN_OK;
-    if (qm_too_many_queries(n_query)) return QMANN_ERANGE;
+    size_t lds;
+    if (const int rc = ham_prepare(a, lds, net, keys, vals, hop_stride, hop_stride, row_off, max_slots, u0, u_out, taps, n_query, hints); rc != kHamGo) return rc;
     hipStream_t st = (hipStream_t)stream;
     const bool mq = a.ham_kinds != 0;                       // some hop's operands leave the attention grid (EN_MQ): the kernels
                                                             // that carry all three lane sums (ham_common.h)
     qm_dispatch<64, 128, 256>(a.Dp, [&](auto dp) {
         constexpr int DP = decltype(dp)::value;
-        if (mq) launch_ham<kModeAppxMq, 8, DP, DP / 16>(a, lds, max_slots, n_query, st);
-        else launch_ham<kModeAppx, 8, DP, DP / 16>(a, lds, max_slots, n_query, st);
+        if (mq) launch_ham<kModeAppxMq, 8, DP, DP / 16>(a, lds, max_slots, n_query, st, hints);
+        else launch_ham<kModeAppx, 8, DP, DP / 16>(a, lds, max_slots, n_query, st, hints);
     });
     QM_LAUNCH_CHECK();
     return qm_scope.rc();
 }
 
-// V0 / V1 straight from sign-magnitude int8 keys (called from qmann_hops_i8)
-int qmann_hops_hambytes_impl(const qmann_net *net, const int8_t *keys, const int8_t *vals, size_t hop_stride,
-                             const uint32_t *row_off, uint32_t max_slots, const float *u0, float *u_out,
-                             const qmann_taps *taps, uint32_t n_query, void *stream)
+// V0 / V1 straight from sign-magnitude int8 keys (called from qm_hops_i8)
+int qmann_hops_hambytes_impl(const qmann_net *net, const int8_t *keys, const int8_t *vals, size_t hop_stride, const uint32_t *row_off, uint32_t max_slots,
+                             const float *u0, float *u_out, const qmann_taps *taps, uint32_t n_query, void *stream, const QmHopHints &hints)
 {
     QmBatched qm_scope;
     const uint32_t nb = net->num_bit, Dp = net->dim_emb_pad;
     if (nb != 1 && nb != 2 && nb != 4 && nb != 8) return QMANN_EUNSUPPORTED;
     HopArgs a;
-    if (const int rc = fill_ham_args(a, net, keys, vals, hop_stride, hop_stride, row_off, u0, u_out, taps)) return rc;
-    a.max_slots = max_slots;
+    size_t lds;
+    if (const int rc = ham_prepare(a, lds, net, keys, vals, hop_stride, hop_stride, row_off, max_slots, u0, u_out, taps, n_query, hints); rc != kHamGo) return rc;
     const bool v1 = net->attention_mode == QMANN_ATT_HAMMING_V1;
-    const size_t lds = ham_lds_bytes(max_slots, v1 ? 0u : nb * net->dim_emb + 1u);
-    if (lds > 160 * 1024 - 1024) return QMANN_ERANGE;
-    if (n_query == 0) return QMANN_OK;
-    if (qm_too_many_queries(n_query)) return QMANN_ERANGE;
     hipStream_t st = (hipStream_t)stream;
     qm_dispatch<64, 128, 256>(Dp, [&](auto dp) {
         qm_dispatch<1, 2, 4, 8>(nb, [&](auto n) {
             constexpr int DP = decltype(dp)::value, NB = decltype(n)::value;
-            if (v1) launch_ham<kModeV1Bytes, NB, DP, DP / 16>(a, lds, max_slots, n_query, st);
-            else launch_ham<kModeV0Bytes, NB, DP, DP / 16>(a, lds, max_slots, n_query, st);
+            if (v1) launch_ham<kModeV1Bytes, NB, DP, DP / 16>(a, lds, max_slots, n_query, st, hints);
+            else launch_ham<kModeV0Bytes, NB, DP, DP / 16>(a, lds, max_slots, n_query, st, hints);
         });
     });
     QM_LAUNCH_CHECK();
     return qm_scope.rc();
 }
 
-int qmann_hops_packed(const qmann_net *net, const uint64_t *key_planes, size_t key_hop_stride, const int8_t *vals,
-                      size_t val_hop_stride, const uint32_t *row_off, uint32_t max_slots, const float *u0,
-                      float *u_out, const qmann_taps *taps, uint32_t n_query, void *stream)
+}  // extern "C"
+
+int qm_hops_packed(const qmann_net *net, const uint64_t *key_planes, size_t key_hop_stride, const int8_t *vals, size_t val_hop_stride, const uint32_t *row_off,
+                   uint32_t max_slots, const float *u0, float *u_out, const qmann_taps *taps, uint32_t n_query, void *stream, const QmHopHints &hints)
 {
     QmBatched qm_scope;
     if (!net) return QMANN_EINVAL;
@@ -398,21 +400,17 @@ int qmann_hops_packed(const qmann_net *net, const uint64_t *key_planes, size_t k
     if (key_hop_stride != val_hop_stride / Dp * (Dp / 64) * nb * 8) return QMANN_EINVAL;
     if (taps && val_hop_stride == 0) return QMANN_EINVAL;   // taps are indexed [hop][row]: they need distinct hop planes
     HopArgs a;
-    if (const int rc = fill_ham_args(a, net, key_planes, vals, key_hop_stride, val_hop_stride, row_off, u0, u_out, taps)) return rc;
-    a.max_slots = max_slots;
+    size_t lds;
+    const int half_row = Dp / 64 * nb * 8 < 16 ? QMANN_EUNSUPPORTED : QMANN_OK;      // Dp = 64 with a single plane: a key row is half a 16-byte load
+    if (const int rc = ham_prepare(a, lds, net, key_planes, vals, key_hop_stride, val_hop_stride, row_off, max_slots, u0, u_out, taps, n_query, hints, half_row); rc != kHamGo) return rc;
     const bool v1 = net->attention_mode == QMANN_ATT_HAMMING_V1;
-    const size_t lds = ham_lds_bytes(max_slots, v1 ? 0u : nb * net->dim_emb + 1u);
-    if (lds > 160 * 1024 - 1024) return QMANN_ERANGE;
-    if (Dp / 64 * nb * 8 < 16) return QMANN_EUNSUPPORTED;      // Dp = 64 with a single plane: a key row is half a 16-byte load
-    if (n_query == 0) return QMANN_OK;
-    if (qm_too_many_queries(n_query)) return QMANN_ERANGE;
     hipStream_t st = (hipStream_t)stream;
     qm_dispatch<64, 128, 256>(Dp, [&](auto dp) {
         qm_dispatch<1, 2, 4, 8>(nb, [&](auto n) {
             constexpr int DP = decltype(dp)::value, NB = decltype(n)::value, LPRK = (DP / 64) * NB * 8 / 16;
             if constexpr (LPRK >= 1) {                      // (no instantiation for the case refused above)
-                if (v1) launch_ham<kModeV1, NB, DP, LPRK>(a, lds, max_slots, n_query, st);
-                else launch_ham<kModeV0, NB, DP, LPRK>(a, lds, max_slots, n_query, st);
+                if (v1) launch_ham<kModeV1, NB, DP, LPRK>(a, lds, max_slots, n_query, st, hints);
+                else launch_ham<kModeV0, NB, DP, LPRK>(a, lds, max_slots, n_query, st, hints);
             }
         });
     });
@@ -420,4 +418,8 @@ int qmann_hops_packed(const qmann_net *net, const uint64_t *key_planes, size_t k
     return qm_scope.rc();
 }
 
-}  // extern "C"
+extern "C" int qmann_hops_packed(const qmann_net *net, const uint64_t *key_planes, size_t key_hop_stride, const int8_t *vals, size_t val_hop_stride,
+                                 const uint32_t *row_off, uint32_t max_slots, const float *u0, float *u_out, const qmann_taps *taps, uint32_t n_query, void *stream)
+{
+    return qm_hops_packed(net, key_planes, key_hop_stride, vals, val_hop_stride, row_off, max_slots, u0, u_out, taps, n_query, stream, QmHopHints{});
+}

@@ -216,8 +216,7 @@ int qmann_hops_shared_i8(const qmann_net *net, const int8_t *keys, const int8_t 
     if (n_query == 0) return QMANN_OK;
     if (qm_too_many_queries(n_query)) return QMANN_ERANGE;
 
-    bool w7 = !qm_tuning().no_w7;
-    for (uint32_t h = 0; h < net->n_hop; h++) w7 = w7 && net->att[h].iwl + net->att[h].frac == 7;
+    const bool w7 = !qm_tuning().no_w7 && all_w7(a, kW7Att);
     const uint32_t qt = choose_qt(n_slots, n_query), per_q = (uint32_t)qmann_hops_lds_bytes(n_slots);
     qm_dispatch<4, 8, 16>(net->dim_emb_pad / 16, [&](auto lpr) {
         qm_dispatch<1, 2, 4, 8>(qt, [&](auto t) {

@@ -35,8 +35,23 @@ struct HopArgs {
 }  // namespace qmann
 using qmann::HopArgs;
 
+// float attention on the HopArgs that qmann_hops_i8 has checked and filled (batch_hops_float.hip)
+extern "C" int qmann_hops_float_impl(const HopArgs &a, uint32_t Dp, uint32_t max_slots, uint32_t n_query, void *stream);
+
 namespace {
 
+// "Every format of the launch has word length 7", over the formats a kernel form asks it of: attention, linear map (where the
+// net has one), activation
+enum : unsigned { kW7Att = 1u, kW7Lin = 2u, kW7Act = 4u };
+inline bool all_w7(const HopArgs &a, unsigned which)
+{
+    for (uint32_t h = 0; h < a.n_hop; h++) {
+        if ((which & kW7Att) && a.att[h].iwl + a.att[h].frac != 7) return false;
+        if ((which & kW7Lin) && a.en_lin_map && a.w[h].iwl + a.w[h].frac != 7) return false;
+        if ((which & kW7Act) && a.act[h].iwl + a.act[h].frac != 7) return false;
+    }
+    return true;
+}
 
 constexpr int kWave = 64;
 constexpr int kBlock = 256;

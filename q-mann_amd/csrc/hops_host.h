@@ -3,6 +3,12 @@
 #pragma once
 #include "hops_lean.h"
 
+// qm_hops_i8's attention families on sign-magnitude int8 keys (batch_hops_ham.hip): APPX, Hamming V0 / V1
+extern "C" int qmann_hops_appx_impl(const qmann_net *net, const int8_t *keys, const int8_t *vals, size_t hop_stride, const uint32_t *row_off, uint32_t max_slots,
+                                    const float *u0, float *u_out, const qmann_taps *taps, uint32_t n_query, void *stream, const QmHopHints &hints);
+extern "C" int qmann_hops_hambytes_impl(const qmann_net *net, const int8_t *keys, const int8_t *vals, size_t hop_stride, const uint32_t *row_off, uint32_t max_slots,
+                                        const float *u0, float *u_out, const qmann_taps *taps, uint32_t n_query, void *stream, const QmHopHints &hints);
+
 namespace {
 
 // the pointers and sizes of a hop call (the first checks of every entry point, ahead of those of its attention family)
@@ -16,16 +22,11 @@ inline int check_hop_call(const qmann_net *net, const void *keys, const int8_t *
     return QMANN_OK;
 }
 
-// A hop call checked (check_hop_call, then the softmax base and the formats) and HopArgs filled from the net -- all but
-// max_slots, which the entry point sets with its LDS size.  `family_check`: what an attention family asks of hop h besides,
-// between the hop's format check and its linear-map check (batch_hops_ham.hip::check_ham_hop).
-// (qmann_hops_i8 has already run check_hop_call, ahead of its taps check and its dispatch by attention mode, to keep the order
-// of its return codes; running it again here costs four compares and keeps this function whole for every other caller.)
-inline int fill_hop_args(HopArgs &a, const qmann_net *net, const void *keys, const int8_t *vals, size_t key_hop_stride,
-                         size_t val_hop_stride, const uint32_t *row_off, const float *u0, float *u_out, const qmann_taps *taps,
-                         int (*family_check)(const qmann_net *, uint32_t) = nullptr)
+// The format half of HopArgs: the softmax base and the formats checked, then every field that is no pointer, stride or size.
+// `family_check`: what an attention family asks of hop h besides (batch_hops_ham.hip::check_ham_hop), between the hop's format
+// check and its linear-map check.
+inline int fill_hop_formats(HopArgs &a, const qmann_net *net, int (*family_check)(const qmann_net *, uint32_t) = nullptr)
 {
-    if (const int rc = check_hop_call(net, keys, vals, row_off, u0, u_out)) return rc;
     if (net->softmax_base > QMANN_SOFTMAX_EXP_PLAN) return QMANN_EINVAL;
     if (!qm_fmt8(net->bin) && net->bin.iwl + net->bin.frac != 0) return QMANN_ERANGE;     // (0,0) = BINARY_MODE: u binarised
     for (uint32_t h = 0; h < net->n_hop; h++) {
@@ -35,14 +36,6 @@ inline int fill_hop_args(HopArgs &a, const qmann_net *net, const void *keys, con
         if (net->en_lin_map && !net->lin_map[h]) return QMANN_EINVAL;
     }
     a = HopArgs{};
-    a.keys = (const int8_t *)keys; a.vals = vals; a.row_off = row_off;
-    a.hop_stride = val_hop_stride; a.key_hop_stride = key_hop_stride;
-    a.u0 = u0; a.u_out = u_out;
-    if (taps) {
-        a.tap_codes = taps->score_codes; a.tap_scores = taps->scores; a.tap_probs = taps->probs;
-        a.tap_o = taps->o; a.tap_u = taps->u;
-    }
-    a.rows_total = val_hop_stride ? (uint32_t)(val_hop_stride / net->dim_emb_pad) : (uint32_t)qm_rows_hint;   // (tied hops: the caller's hint, or 0 = unknown)
     a.n_hop = net->n_hop; a.D = net->dim_emb; a.Dp = net->dim_emb_pad;
     a.softmax_base = net->softmax_base; a.en_lin_map = net->en_lin_map;
     a.softmax_shift = net->softmax_shift_based; a.en_att_scale = net->en_att_scale; a.en_non_lin = net->en_non_linearity;
@@ -57,18 +50,70 @@ inline int fill_hop_args(HopArgs &a, const qmann_net *net, const void *keys, con
     return QMANN_OK;
 }
 
-// The kernel of a hop launch by memory size: up to 64 slots the lean kernel (hops_lean.h) where it covers the call -- not for
-// packed planes, which have no lean form -- else one wavefront per query (hops_small.h); `general` launches longer memories.
-// LPR / LPRK: lanes per value / key row; key_row_bytes: 16 LPRK
+// A hop call checked (check_hop_call, then fill_hop_formats) and HopArgs filled -- all but max_slots, which the entry point sets
+// with its LDS size.  `plane_rows`: rt.h::QmHopHints, the plane's size for calls with val_hop_stride = 0.
+// (qmann_hops_i8 has already run check_hop_call, ahead of its taps check and its dispatch by attention mode, to keep the order
+// of its return codes; running it again here costs four compares and keeps this function whole for every other caller.)
+inline int fill_hop_args(HopArgs &a, const qmann_net *net, const void *keys, const int8_t *vals, size_t key_hop_stride,
+                         size_t val_hop_stride, const uint32_t *row_off, const float *u0, float *u_out, const qmann_taps *taps,
+                         size_t plane_rows = 0, int (*family_check)(const qmann_net *, uint32_t) = nullptr)
+{
+    if (const int rc = check_hop_call(net, keys, vals, row_off, u0, u_out)) return rc;
+    if (const int rc = fill_hop_formats(a, net, family_check)) return rc;
+    a.keys = (const int8_t *)keys; a.vals = vals; a.row_off = row_off;
+    a.hop_stride = val_hop_stride; a.key_hop_stride = key_hop_stride;
+    a.u0 = u0; a.u_out = u_out;
+    if (taps) {
+        a.tap_codes = taps->score_codes; a.tap_scores = taps->scores; a.tap_probs = taps->probs;
+        a.tap_o = taps->o; a.tap_u = taps->u;
+    }
+    a.rows_total = (uint32_t)(val_hop_stride ? val_hop_stride / net->dim_emb_pad : plane_rows);   // (tied hops: the caller's hint, or 0 = unknown)
+    return QMANN_OK;
+}
+
+// The ONE decision of a hop launch: the form it takes.  No HIP call, no state but qm_tuning(): asking twice gives the same
+// answer, which is how the host model knows ahead of the launch that a batch will be split (batch_hops.hip::qm_hops_will_split).
+// Up to 64 slots the lean kernels where they cover the call -- not for packed planes, which have no lean form -- else one
+// wavefront per query; longer memories: hops_mid.h where it covers them, else the family's general kernel.
+inline HopPlan hop_plan(const HopArgs &a, int mode, uint32_t key_row_bytes, uint32_t max_slots, uint32_t n_query)
+{
+    // (known from the plane size; tied hops without a hint carry none and take the bAbI guess: stories short next to their cap)
+    const uint32_t mean_slots = (a.rows_total && n_query) ? a.rows_total / n_query : max_slots / 8u;
+    auto plan = [&](HopForm f) { return HopPlan{f, mean_slots}; };
+    if (mode_is_planes(mode) || !lean_supported(a, max_slots, key_row_bytes)) {
+        if (max_slots <= (uint32_t)kWave) return plan(HopForm::Small);
+        return plan(mode == kModeFixed && mid_supported(a, max_slots) ? HopForm::Mid : HopForm::General);    // hops_mid.h: 65 .. 1 024 slots at bAbI width
+    }
+    // Small batches keep one story per wavefront: the GPU holds 6 144 wavefronts at once, so up to a few thousand stories each has
+    // one of its own and the batch takes ONE story's latency, where four stories per wavefront take their linear maps in turn
+    // (task-1 forward, interleaved: 256 stories 34.8 -> 27.2 us, 1 024 36.8 -> 29.3, 4 096 40.4 -> 38.9, 8 192 53.7 -> 50.0,
+    // 16 384 72.1 <- 75.2: the quad form from there on; 64-story serving batches replayed from a graph 39.2 -> 31.1 us)
+    if (!quad_supported(a, mode, max_slots, n_query) || n_query <= qm_tuning().quad_min_queries) return plan(HopForm::Lean);
+    if (max_slots <= kQuadSlots) return plan(HopForm::Quad);
+    // A batch is split only where short stories can be many: mean length within the short form's 16 rows.  A batch of long
+    // stories -- the |mem| = 50 shape of BASELINE's metric -- goes whole through the four-chunk form (QMANN_NO_QUAD_LONG: the lean kernel).
+    if (mean_slots > kQuadSlots)
+        // (fixed-point scores only: the form is 2 % ahead of the lean kernel at 50 rows -- 7 % fewer vector instructions per query,
+        // four wavefronts per SIMD against six -- which does not pay for ten more instantiations in the Hamming modes)
+        return plan(mode == kModeFixed && !qm_tuning().no_quad_long ? HopForm::QuadLong : HopForm::Lean);
+    return plan(HopForm::Split);
+}
+
+// One hop launch by its plan (the cases in the order their kernels have always been instantiated: tools/device_asm_equal.sh).
+// `general(form)` launches long memories: HopForm::General, or Mid -- planned for fixed-point scores only, whose entry point
+// has hops_mid.h.  LPR / LPRK: lanes per value / key row; key_row_bytes: 16 LPRK
 template <int MODE, int NB, int LPR, int LPRK, typename General>
-inline void launch_hops(const HopArgs &a, uint32_t max_slots, uint32_t n_query, hipStream_t st, General &&general)
+inline void launch_hops(const HopArgs &a, uint32_t max_slots, uint32_t n_query, hipStream_t st, const QmHopHints &hints, General &&general)
 {
     constexpr uint32_t key_row_bytes = 16u * LPRK;
-    if constexpr (!mode_is_planes(MODE)) {
-        if (lean_supported(a, max_slots, key_row_bytes)) { launch_lean<MODE, NB>(a, max_slots, n_query, st); return; }
+    const HopPlan plan = hop_plan(a, MODE, key_row_bytes, max_slots, n_query);
+    switch (plan.form) {
+    case HopForm::Lean: case HopForm::Quad: case HopForm::QuadLong: case HopForm::Split:
+        if constexpr (!mode_is_planes(MODE)) launch_lean<MODE, NB>(a, plan, max_slots, n_query, st, hints.split_ws);
+        break;
+    case HopForm::Small: k_hops_small<LPR, LPRK, MODE, NB><<<n_query, kWave, 0, st>>>(a, key_row_bytes); break;
+    case HopForm::Mid: case HopForm::General: general(plan.form); break;
     }
-    if (max_slots <= (uint32_t)kWave) k_hops_small<LPR, LPRK, MODE, NB><<<n_query, kWave, 0, st>>>(a, key_row_bytes);
-    else general();
 }
 
 }  // namespace

@@ -590,6 +590,18 @@ inline bool lean_supported(const HopArgs &a, uint32_t max_slots, uint32_t key_ro
            !a.tap_o && !a.tap_u && !qm_tuning().no_lean;
 }
 
+constexpr uint32_t kMidMaxSlots = 1024;
+// what hops_mid.h::k_hops_mid covers (here, beside lean_supported, for hops_host.h::hop_plan: a unit that includes hops_mid.h
+// instantiates its kernels): fixed-point attention with the softmax's exponential from a table -- e^x, or the CPU softmax's 2^x /
+// exp_plan with its serial float total (no shift-based form, no scale layer),
+// 64-byte rows, 65 .. 1 024 slots, no taps; everything else keeps the streaming kernel
+inline bool mid_supported(const HopArgs &a, uint32_t max_slots)
+{
+    return a.Dp == 64 && max_slots > (uint32_t)kWave && max_slots <= kMidMaxSlots && a.softmax_base <= QMANN_SOFTMAX_EXP_PLAN &&
+           !a.softmax_shift && !a.en_att_scale && !a.tap_codes && !a.tap_scores && !a.tap_probs && !a.tap_o && !a.tap_u &&
+           !qm_tuning().no_mid;
+}
+
 template <int MODE, int NB, bool W7, bool SPARSE>
 inline void launch_lean_w(HopArgs a, uint32_t max_slots, uint32_t n_query, hipStream_t st, const uint32_t *list = nullptr,
                           const uint32_t *n_list = nullptr, const uint32_t *n_other = nullptr)
@@ -619,51 +631,38 @@ inline void launch_lean_w(HopArgs a, uint32_t max_slots, uint32_t n_query, hipSt
     else go(k_hops_lean<MODE, NB, W7, SPARSE, kLeanWpsWide>, kLeanWpsWide);
 }
 
+// The form a hop launch takes (hops_host.h::hop_plan decides; launch_hops and launch_lean switch over it) and the mean story
+// length the decision went by.  Small: one wavefront per query (hops_small.h); Lean: the lean kernel over the whole batch;
+// Quad / QuadLong: four queries per wavefront (hops_quad.h), stories of <= 16 rows in one chunk / 17 .. 64 rows in four;
+// Split: Quad over the batch's short stories, Lean over its long ones; Mid: hops_mid.h; General: the family's long-memory kernel
+enum class HopForm { Small, Lean, Quad, QuadLong, Split, Mid, General };
+struct HopPlan { HopForm form; uint32_t mean_slots; };
+
 template <int MODE, int NB>
-inline void launch_lean_all(const HopArgs &a, uint32_t max_slots, uint32_t n_query, hipStream_t st, const uint32_t *list = nullptr,
-                            const uint32_t *n_list = nullptr, const uint32_t *n_other = nullptr);
+inline void launch_lean_all(const HopArgs &a, uint32_t mean_slots, uint32_t max_slots, uint32_t n_query, hipStream_t st,
+                            const uint32_t *list = nullptr, const uint32_t *n_list = nullptr, const uint32_t *n_other = nullptr);
 
 // Short-memory launches: stories of at most 16 rows take the four-queries-per-wavefront kernel (hops_quad.h), longer ones the
 // one-wavefront-per-query kernel below.  A batch whose bound allows both (the 20-task set: up to 64 rows, 91 % of the stories
 // <= 16) is split on the device into two index lists first (k_split_by_length); the two kernels then run each over its list --
 // one after the other on the stream, or side by side on two streams where that pays (below).  Batches of at most
 // QMANN_QUAD_MIN_QUERIES stories keep one story per wavefront.  QMANN_NO_QUAD keeps everything on the lean kernel (A/B).
+// `split_ws`: the lists of a Split plan where the caller has made them already (rt.h::QmHopHints), else null.
 template <int MODE, int NB>
-inline void launch_lean(const HopArgs &a, uint32_t max_slots, uint32_t n_query, hipStream_t st)
+inline void launch_lean(const HopArgs &a, const HopPlan &plan, uint32_t max_slots, uint32_t n_query, hipStream_t st, uint32_t *split_ws)
 {
-    // Small batches keep one story per wavefront: the GPU holds 6 144 wavefronts at once, so up to a few thousand stories each has
-    // one of its own and the batch takes ONE story's latency, where four stories per wavefront take their linear maps in turn
-    // (task-1 forward, interleaved: 256 stories 34.8 -> 27.2 us, 1 024 36.8 -> 29.3, 4 096 40.4 -> 38.9, 8 192 53.7 -> 50.0,
-    // 16 384 72.1 <- 75.2: the quad form from there on; 64-story serving batches replayed from a graph 39.2 -> 31.1 us)
-    if (!quad_supported(a, MODE, max_slots, n_query) || n_query <= qm_tuning().quad_min_queries) {
-        launch_lean_all<MODE, NB>(a, max_slots, n_query, st);
+    const QuadArgs whole{nullptr, nullptr, n_query, nullptr, nullptr};
+    switch (plan.form) {
+    case HopForm::Lean: launch_lean_all<MODE, NB>(a, plan.mean_slots, max_slots, n_query, st); return;
+    case HopForm::Quad: launch_quad<MODE, NB, 1>(a, whole, n_query, st); return;
+    case HopForm::QuadLong:
+        if constexpr (MODE == kModeFixed) launch_quad<MODE, NB, 4>(a, whole, n_query, st);
+        else launch_lean_all<MODE, NB>(a, plan.mean_slots, max_slots, n_query, st);             // (never planned: hop_plan gives this form to fixed-point scores only)
         return;
+    default: break;                                                                              // HopForm::Split, the rest of this function
     }
-    if (max_slots <= kQuadSlots) {
-        launch_quad<MODE, NB, 1>(a, QuadArgs{nullptr, nullptr, n_query, nullptr, nullptr}, n_query, st);
-        return;
-    }
-    // A batch is split only where short stories can be many: mean length (known from the plane size; tied hops carry none and
-    // take the bAbI guess, stories short next to their cap) within the short form's 16 rows.  A batch of long stories -- the
-    // |mem| = 50 shape of BASELINE's metric -- goes whole through the four-chunk form (QMANN_NO_QUAD_LONG: the lean kernel).
-    const uint32_t mean_slots = (a.rows_total && n_query) ? a.rows_total / n_query : max_slots / 8u;
-    if (mean_slots > kQuadSlots) {
-        // (fixed-point scores only: the form is 2 % ahead of the lean kernel at 50 rows -- 7 % fewer vector instructions per query,
-        // four wavefronts per SIMD against six -- which does not pay for ten more instantiations in the Hamming modes)
-        if constexpr (MODE == kModeFixed) {
-            if (!qm_tuning().no_quad_long) { launch_quad<MODE, NB, 4>(a, QuadArgs{nullptr, nullptr, n_query, nullptr, nullptr}, n_query, st); return; }
-        }
-        launch_lean_all<MODE, NB>(a, max_slots, n_query, st);
-        return;
-    }
-    uint32_t *ws = nullptr;
-    {
-        const QmSplitReady r = qm_split_ready;                                // (prepared by the host model beside the story embedding)
-        qm_split_ready = QmSplitReady{nullptr, 0, 0, nullptr};
-        if (r.ws && r.row_off == a.row_off && r.n_query == n_query && r.max_slots == max_slots) ws = r.ws;
-    }
-    if (!ws) ws = split_lists(a.row_off, n_query, max_slots, st, st);
-    if (!ws) { launch_lean_all<MODE, NB>(a, max_slots, n_query, st); return; }
+    uint32_t *ws = split_ws ? split_ws : split_lists(a.row_off, n_query, max_slots, st, st);
+    if (!ws) { launch_lean_all<MODE, NB>(a, plan.mean_slots, max_slots, n_query, st); return; }
     // Large batches: the two kernels SIDE BY SIDE -- the long stories' kernel on a second stream (forked and joined by events, so
     // the caller's stream sees one ordered step and a stream capture takes both branches).  Both are bound by vector issue and
     // latency, not by a shared unit: together they fill the issue slots either leaves empty alone.  How the CUs' room is divided
@@ -689,7 +688,7 @@ inline void launch_lean(const HopArgs &a, uint32_t max_slots, uint32_t n_query, 
         if (pays) {
             QM_HIP(hipEventRecord(sd->fork, st));
             QM_HIP(hipStreamWaitEvent(sd->side, sd->fork, 0));
-            launch_lean_all<MODE, NB>(a, max_slots, n_query, sd->side, ws + 2 + n_query, ws + 1, ws);
+            launch_lean_all<MODE, NB>(a, plan.mean_slots, max_slots, n_query, sd->side, ws + 2 + n_query, ws + 1, ws);
             QM_HIP(hipEventRecord(sd->join, sd->side));
             launch_quad<MODE, NB, 1>(a, QuadArgs{ws + 2, ws, n_query, ws + 1, publish}, n_query, st);
             QM_HIP(hipStreamWaitEvent(st, sd->join, 0));
@@ -698,17 +697,14 @@ inline void launch_lean(const HopArgs &a, uint32_t max_slots, uint32_t n_query, 
     }
     launch_quad<MODE, NB, 1>(a, QuadArgs{ws + 2, ws, n_query, nullptr, publish}, n_query, st);
     // (the few long stories of such a batch: the lean kernel -- the four-chunk quad form measured 3 % SLOWER on the joint forward)
-    launch_lean_all<MODE, NB>(a, max_slots, n_query, st, ws + 2 + n_query, ws + 1);
+    launch_lean_all<MODE, NB>(a, plan.mean_slots, max_slots, n_query, st, ws + 2 + n_query, ws + 1);
 }
 
 template <int MODE, int NB>
-inline void launch_lean_all(const HopArgs &a, uint32_t max_slots, uint32_t n_query, hipStream_t st, const uint32_t *list, const uint32_t *n_list,
-                            const uint32_t *n_other)
+inline void launch_lean_all(const HopArgs &a, uint32_t mean_slots, uint32_t max_slots, uint32_t n_query, hipStream_t st, const uint32_t *list,
+                            const uint32_t *n_list, const uint32_t *n_other)
 {
-    bool w7 = true;
-    for (uint32_t h = 0; h < a.n_hop; h++)
-        w7 = w7 && (MODE != kModeFixed || a.att[h].iwl + a.att[h].frac == 7) && (!a.en_lin_map || a.w[h].iwl + a.w[h].frac == 7) &&
-             a.act[h].iwl + a.act[h].frac == 7;
+    const bool w7 = all_w7(a, (MODE == kModeFixed ? kW7Att : 0u) | kW7Lin | kW7Act);
     // Sparse read-out (only the value rows that survive Q(p) are fetched, lean_hop) where those rows -- at most 2^frac_act per
     // hop -- are a small part of the longest story; otherwise the whole value tile is copied to LDS at the start of the hop.
     // QMANN_LEAN_SPARSE=0 / 1 forces the choice (A/B).
@@ -717,7 +713,6 @@ inline void launch_lean_all(const HopArgs &a, uint32_t max_slots, uint32_t n_que
     // the linear map): the choice goes by the MEAN story length, which the launch knows from the plane size.
     uint32_t surv = 1;
     for (uint32_t h = 0; h < a.n_hop; h++) surv = surv > (1u << a.act[h].frac) ? surv : (1u << a.act[h].frac);
-    uint32_t mean_slots = (a.rows_total && n_query) ? a.rows_total / n_query : max_slots / 8u;     // (tied hops: no plane size; real stories are short next to their cap)
     if (list) mean_slots = mean_slots > kQuadSlots + 1u ? mean_slots : kQuadSlots + 1u;          // (the long stories of a split batch: each has > 16 rows)
     bool sparse = surv * 4u <= mean_slots;
     // ... and wherever the value tiles would cost a workgroup per CU: 8 wavefronts x 64 rows x 64 bytes = 32 KB of tiles leave

@@ -20,13 +20,12 @@
 // a histogram sum (count . e per score code) there -- equal to the last bit or two of a double, which shows only where a weight
 // sits exactly on a truncation step of Q(p) (two tied top scores at one or two fraction bits: 1 in ~240 random-format soak
 // cases; tools/soak.py reports the count).  Neither order is the reference's serial one (lib/layer_cuda.cu:2024); the oracle
-// sums serially and such cases are the ones the tests excuse with the oracle's evidence that a p lies on a step.  Taken by qmann_hops_i8 for 64 < max_slots <= 1 024 when mid_supported() holds.
+// sums serially and such cases are the ones the tests excuse with the oracle's evidence that a p lies on a step.  Taken by qmann_hops_i8 for 64 < max_slots <= 1 024 when hops_lean.h::mid_supported() holds.
 #pragma once
 #include "hops_lean.h"
 
 namespace {
 
-constexpr uint32_t kMidMaxSlots = 1024;
 #ifndef QM_MID_WAVES
 #define QM_MID_WAVES 8                                    // (10 -- five wavefronts per SIMD at 96 registers -- measured 35 % slower)
 #endif
@@ -203,16 +202,6 @@ k_hops_mid(const HopArgs a, const LeanArgs la)
     }
 }
 
-// what this kernel covers: fixed-point attention with the softmax's exponential from a table -- e^x, or the CPU softmax's 2^x /
-// exp_plan with its serial float total (no shift-based form, no scale layer),
-// 64-byte rows, 65 .. 1 024 slots, no taps; everything else keeps the streaming kernel
-inline bool mid_supported(const HopArgs &a, uint32_t max_slots)
-{
-    return a.Dp == 64 && max_slots > (uint32_t)kWave && max_slots <= kMidMaxSlots && a.softmax_base <= QMANN_SOFTMAX_EXP_PLAN &&
-           !a.softmax_shift && !a.en_att_scale && !a.tap_codes && !a.tap_scores && !a.tap_probs && !a.tap_o && !a.tap_u &&
-           !qm_tuning().no_mid;
-}
-
 template <bool W7>
 inline void launch_mid_w(HopArgs a, uint32_t max_slots, uint32_t n_query, hipStream_t st)
 {
@@ -228,10 +217,7 @@ inline void launch_mid_w(HopArgs a, uint32_t max_slots, uint32_t n_query, hipStr
 
 inline void launch_mid(const HopArgs &a, uint32_t max_slots, uint32_t n_query, hipStream_t st)
 {
-    bool w7 = true;
-    for (uint32_t h = 0; h < a.n_hop; h++)
-        w7 = w7 && a.att[h].iwl + a.att[h].frac == 7 && (!a.en_lin_map || a.w[h].iwl + a.w[h].frac == 7) &&
-             a.act[h].iwl + a.act[h].frac == 7;                       // (lean_finish_hop<true> folds every word length to 7)
+    const bool w7 = all_w7(a, kW7Att | kW7Lin | kW7Act);                // (lean_finish_hop<true> folds every word length to 7)
     qm_dispatch<false, true>(w7, [&](auto w) { launch_mid_w<decltype(w)::value>(a, max_slots, n_query, st); });
 }
 

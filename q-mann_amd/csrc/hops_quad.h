@@ -461,7 +461,7 @@ k_split_by_length(const uint32_t *__restrict__ row_off, uint32_t n_query, uint32
 }
 
 // [0] short count, [1] long count, then the two lists (n_query words each), in the scratch words of stream `owner`; the work
-// itself goes to `run_on` (the same stream, or the second one beside it -- rt.h::QmSplitReady)
+// itself goes to `run_on` (the same stream, or the second one beside it -- rt.h::qm_split_early)
 inline uint32_t *split_lists(const uint32_t *row_off, uint32_t n_query, uint32_t max_slots, hipStream_t owner, hipStream_t run_on)
 {
     uint32_t *ws = qm_scratch_u32(2u + 2u * (size_t)n_query, owner);
@@ -477,15 +477,10 @@ inline uint32_t *split_lists(const uint32_t *row_off, uint32_t n_query, uint32_t
 inline bool quad_supported(const HopArgs &a, int mode, uint32_t max_slots, uint32_t n_query)
 {
     if (qm_tuning().no_quad || a.softmax_base != QMANN_SOFTMAX_EXP || a.softmax_shift) return false;
-    for (uint32_t h = 0; h < a.n_hop; h++) {
-        if (a.act[h].iwl + a.act[h].frac != 7) return false;
-        if (mode == kModeFixed && a.att[h].iwl + a.att[h].frac != 7) return false;
-        if (a.en_lin_map && a.w[h].iwl + a.w[h].frac != 7) return false;
-    }
-    if (a.bin.frac > 7u) return false;
+    if (!all_w7(a, (mode == kModeFixed ? kW7Att : 0u) | kW7Lin | kW7Act) || a.bin.frac > 7u) return false;
     // The kernel addresses rows by 32-bit byte offsets from the start of a hop's plane (one buffer resource per hop): the plane --
     // every row the batch's offsets can name, cut stories' unused rows included -- must stay below 2 GiB, and its size must be
-    // KNOWN: from hop_stride, or for tied hops (hop_stride = 0) from the caller's hint (rt.h::QmRowsHint, qmann_model gives it)
+    // KNOWN: from hop_stride, or for tied hops (hop_stride = 0) from the caller's hint (rt.h::QmHopHints, qmann_model gives it)
     return a.rows_total != 0u && (uint64_t)a.rows_total * 64u < 0x7FFF0000ull;
 }
 

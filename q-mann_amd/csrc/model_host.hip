@@ -91,6 +91,7 @@ struct qmann_model {
     uint16_t *bow_words = nullptr;
     uint32_t *bow_irr = nullptr;
     size_t cap_rows = 0, cap_plane_words = 0, cap_query = 0, cap_bow = 0;
+    bool answer_exact = false;   // rt.h::qm_model_answer_exact: the float answer layer keeps the serial order of additions
 };
 
 namespace {
@@ -242,24 +243,54 @@ int ensure_float_matrices(qmann_model *m, void *stream)
     return QMANN_OK;
 }
 
-// hops + answer on the memories sitting in the workspace (hop planes rows_total . Dp apart; one shared plane when tied)
+// hops + answer on the memories sitting in the workspace (hop planes rows_total . Dp apart; one shared plane when tied).
+// `split_ws`: the batch's index lists where with_side_branch below has made them, else null.
 int hops_and_answer(qmann_model *m, uint32_t rows_total, const uint32_t *row_off, uint32_t max_slots, uint32_t n_query,
-                    const uint32_t *answer, uint32_t *pred, float *cost, uint32_t *match, void *stream)
+                    const uint32_t *answer, uint32_t *pred, float *cost, uint32_t *match, void *stream, uint32_t *split_ws)
 {
     const size_t hop_stride = m->tied ? 0 : (size_t)rows_total * m->Dp;
-    QmRowsHint plane_rows(rows_total);               // (a tied model passes hop_stride = 0: the hop kernels still learn the plane's size)
+    const QmHopHints hints{rows_total, split_ws};    // (a tied model passes hop_stride = 0: the hop kernels still learn the plane's size)
     int rc;
     if (use_planes(m, max_slots)) {
         const size_t key_hop_stride = m->tied ? 0 : (size_t)rows_total * (m->Dp / 64) * m->net.num_bit * 8;
         rc = qmann_pack_bitplanes(m->keys, m->planes, (size_t)(m->tied ? 1 : m->H) * rows_total, m->Dp, m->net.num_bit, stream);
         if (rc) return rc;
-        rc = qmann_hops_packed(&m->net, m->planes, key_hop_stride, m->vals, hop_stride, row_off, max_slots, m->u0, m->u,
-                               nullptr, n_query, stream);
+        rc = qm_hops_packed(&m->net, m->planes, key_hop_stride, m->vals, hop_stride, row_off, max_slots, m->u0, m->u,
+                            nullptr, n_query, stream, hints);
     } else {
-        rc = qmann_hops_i8(&m->net, m->keys, m->vals, hop_stride, row_off, max_slots, m->u0, m->u, nullptr, n_query, stream);
+        rc = qm_hops_i8(&m->net, m->keys, m->vals, hop_stride, row_off, max_slots, m->u0, m->u, nullptr, n_query, stream, hints);
     }
     if (rc) return rc;
-    return qmann_answer_f32(&m->net, m->w_ans, m->u, answer, pred, nullptr, cost, match, n_query, stream);
+    return (m->answer_exact ? qmann_answer_f32_serial : qmann_answer_f32)(&m->net, m->w_ans, m->u, answer, pred, nullptr, cost, match, n_query, stream);
+}
+
+// The embedding step of a forward: `story(stream)` on the caller's stream and -- for large batches -- `question(side stream)`
+// BESIDE it on a second stream (forked and joined by events: one ordered step to the caller's stream, both branches to a stream
+// capture).  The story kernels are latency-bound persistent grids that leave 32 .. 80 registers per SIMD lane unallocated; the
+// question kernel is built to fit 32 (batch_embed_idx.hip) and is bound by its own stores, so its workgroups run in that room.
+// Launched AFTER the story kernel, so that one keeps its full residency.  Behind the question, still beside the story embedding,
+// the two index lists of a batch that the hop launch will split by story length (rt.h::qm_hops_will_split; they depend on
+// row_off alone; 12 us of memset + kernel + launch gaps off the caller's stream): *split_ws, null where there are none.
+template <typename Story, typename Question>
+int with_side_branch(const qmann_model *m, uint32_t rows_total, const uint32_t *row_off, uint32_t max_slots, uint32_t n_query, void *stream,
+                     uint32_t **split_ws, Story &&story, Question &&question)
+{
+    hipStream_t st = (hipStream_t)stream;
+    QmSide *sd = (n_query >= kQmCorunMinQueries && !qm_tuning().no_corun) ? qm_side_stream(st) : nullptr;
+    if (sd) {
+        QM_HIP(hipEventRecord(sd->fork, st));
+        QM_HIP(hipStreamWaitEvent(sd->side, sd->fork, 0));
+    }
+    const int rc = story(stream);
+    const int rc_q = question(sd ? (void *)sd->side : stream);
+    *split_ws = nullptr;
+    if (sd && !rc_q && !use_planes(m, max_slots) && qm_hops_will_split(&m->net, rows_total, max_slots, n_query))
+        *split_ws = qm_split_early(row_off, n_query, max_slots, st, sd->side);
+    if (sd) {                                            // (joined on every path: a capture must not end with an open branch)
+        QM_HIP(hipEventRecord(sd->join, sd->side));
+        QM_HIP(hipStreamWaitEvent(st, sd->join, 0));
+    }
+    return rc ? rc : rc_q;
 }
 
 int resolve_device(int device, int *out)
@@ -428,30 +459,12 @@ int qmann_model_forward_words(qmann_model *m, const uint16_t *story_words, uint3
     DeviceScope on(m->device);
     int rc = ensure(m, rows_total, n_query, use_planes(m, max_slots));
     if (rc) return rc;
-    // Large batches: the question embedding on a second stream BESIDE the story embedding (forked and joined by events: one ordered
-    // step to the caller's stream, both branches to a stream capture).  The story kernels are latency-bound persistent grids that
-    // leave 32 .. 80 registers per SIMD lane unallocated; the question kernel is built to fit 32 (batch_embed_idx.hip) and is bound by its
-    // own stores, so its workgroups run in that room.  Launched AFTER the story kernel, so that one keeps its full residency.
-    QmSide *sd = (n_query >= kQmCorunMinQueries && !qm_tuning().no_corun) ? qm_side_stream((hipStream_t)stream) : nullptr;
-    if (sd) {
-        QM_HIP(hipEventRecord(sd->fork, (hipStream_t)stream));
-        QM_HIP(hipStreamWaitEvent(sd->side, sd->fork, 0));
-    }
-    rc = qmann_embed_story_idx(&m->emb_net, story_words, rows_total, max_words, 1, m->t_a, m->t_c, m->keys, m->vals,
-                               (size_t)rows_total * m->Dp, stream);
-    const int rc_q = qmann_embed_query_idx(&m->net, question_words, max_q_words, m->t_q, m->u0, n_query, sd ? (void *)sd->side : stream);
-    // ... and behind it, still beside the story embedding, the two index lists of a batch that the hop launch will split by
-    // story length (they depend on row_off alone; 12 us of memset + kernel + launch gaps off the caller's stream)
-    struct SplitScope { ~SplitScope() { qm_split_ready = QmSplitReady{nullptr, 0, 0, nullptr}; } } split_scope;
-    if (sd && !rc_q && qm_split_applies(rows_total, n_query, max_slots))
-        qm_split_ready = QmSplitReady{row_off, n_query, max_slots, qm_split_early(row_off, n_query, max_slots, (hipStream_t)stream, sd->side)};
-    if (sd) {                                            // (joined on every path: a capture must not end with an open branch)
-        QM_HIP(hipEventRecord(sd->join, sd->side));
-        QM_HIP(hipStreamWaitEvent((hipStream_t)stream, sd->join, 0));
-    }
+    uint32_t *split_ws;
+    rc = with_side_branch(m, rows_total, row_off, max_slots, n_query, stream, &split_ws,
+        [&](void *s) { return qmann_embed_story_idx(&m->emb_net, story_words, rows_total, max_words, 1, m->t_a, m->t_c, m->keys, m->vals, (size_t)rows_total * m->Dp, s); },
+        [&](void *s) { return qmann_embed_query_idx(&m->net, question_words, max_q_words, m->t_q, m->u0, n_query, s); });
     if (rc) return rc;
-    if (rc_q) return rc_q;
-    rc = hops_and_answer(m, rows_total, row_off, max_slots, n_query, answer, pred, cost, match, stream);
+    rc = hops_and_answer(m, rows_total, row_off, max_slots, n_query, answer, pred, cost, match, stream, split_ws);
     return rc ? rc : qm_scope.rc();
 }
 
@@ -503,43 +516,36 @@ int qmann_model_forward_bow(qmann_model *m, const float *story, uint32_t rows_to
         if (!ok_w || !ok_i) return QMANN_EHIP;
         m->cap_bow = cap;
     }
-    hipStream_t st = (hipStream_t)stream;
     uint32_t *n_irr = m->bow_irr, *irr_s = m->bow_irr + 2, *irr_q = irr_s + rows_total;
     uint16_t *sw = m->bow_words, *qw = m->bow_words + (size_t)rows_total * 16;
-    QM_HIP(hipMemsetAsync(n_irr, 0, 2 * sizeof(uint32_t), st));
-    // Both conversions first, then -- as in qmann_model_forward_words -- the question embedding and the length split of a mixed
-    // batch on the second stream beside the story embedding.  (The question's CONVERSION beside the story's was measured too:
-    // 0.735 against 0.714 ms on task 1 -- its workgroups sit on the CUs when the story embedding's persistent grid arrives.)
+    QM_HIP(hipMemsetAsync(n_irr, 0, 2 * sizeof(uint32_t), (hipStream_t)stream));
+    // Both conversions first, then the embeddings (with_side_branch: the question's beside the story's).  (The question's
+    // CONVERSION beside the story's was measured too: 0.735 against 0.714 ms on task 1 -- its workgroups sit on the CUs when the
+    // story embedding's persistent grid arrives.)
     const size_t hop_stride = (size_t)rows_total * m->Dp;
     rc = qmann_bow_to_words(story, rows_total, m->V, sw, irr_s, n_irr, stream);
     if (rc) return rc;
     rc = qmann_bow_to_words(question, n_query, m->V, qw, irr_q, n_irr + 1, stream);
     if (rc) return rc;
-    QmSide *sd = (n_query >= kQmCorunMinQueries && !qm_tuning().no_corun) ? qm_side_stream(st) : nullptr;
-    void *qs = sd ? (void *)sd->side : stream;
-    if (sd) {
-        QM_HIP(hipEventRecord(sd->fork, st));
-        QM_HIP(hipStreamWaitEvent(sd->side, sd->fork, 0));
-    }
-    rc = qmann_embed_story_idx(&m->emb_net, sw, rows_total, 16, /*time_last=*/0, m->t_a, m->t_c, m->keys, m->vals, hop_stride, stream);
-    if (!rc) rc = qmann_embed_story_rows(&m->emb_net, story, rows_total, irr_s, n_irr, m->w_a, m->w_c, m->keys, m->vals, hop_stride, stream);
-    qmann_net qnet = m->net;
-    qnet.en_pe = 0;                                     // (position weights, if any, are IN the rows: such rows take the float kernel)
-    int rc_q = qmann_embed_query_idx(&qnet, qw, 16, m->t_q, m->u0, n_query, qs);
-    if (!rc_q) rc_q = qmann_embed_query_rows(&m->net, question, irr_q, n_irr + 1, m->w_q, m->u0, n_query, qs);
-    struct SplitScope { ~SplitScope() { qm_split_ready = QmSplitReady{nullptr, 0, 0, nullptr}; } } split_scope;
-    if (sd && !rc_q && qm_split_applies(rows_total, n_query, max_slots))
-        qm_split_ready = QmSplitReady{row_off, n_query, max_slots, qm_split_early(row_off, n_query, max_slots, st, sd->side)};
-    if (sd) {                                            // (joined on every path: a capture must not end with an open branch)
-        QM_HIP(hipEventRecord(sd->join, sd->side));
-        QM_HIP(hipStreamWaitEvent(st, sd->join, 0));
-    }
+    uint32_t *split_ws;
+    rc = with_side_branch(m, rows_total, row_off, max_slots, n_query, stream, &split_ws,
+        [&](void *s) {
+            const int e = qmann_embed_story_idx(&m->emb_net, sw, rows_total, 16, /*time_last=*/0, m->t_a, m->t_c, m->keys, m->vals, hop_stride, s);
+            return e ? e : qmann_embed_story_rows(&m->emb_net, story, rows_total, irr_s, n_irr, m->w_a, m->w_c, m->keys, m->vals, hop_stride, s);
+        },
+        [&](void *s) {
+            qmann_net qnet = m->net;
+            qnet.en_pe = 0;                             // (position weights, if any, are IN the rows: such rows take the float kernel)
+            const int e = qmann_embed_query_idx(&qnet, qw, 16, m->t_q, m->u0, n_query, s);
+            return e ? e : qmann_embed_query_rows(&m->net, question, irr_q, n_irr + 1, m->w_q, m->u0, n_query, s);
+        });
     if (rc) return rc;
-    if (rc_q) return rc_q;
-    rc = hops_and_answer(m, rows_total, row_off, max_slots, n_query, answer, pred, cost, match, stream);
+    rc = hops_and_answer(m, rows_total, row_off, max_slots, n_query, answer, pred, cost, match, stream, split_ws);
     return rc ? rc : qm_scope.rc();
 }
 
 const float *qmann_model_last_u(const qmann_model *m) { return m ? m->u : nullptr; }
 
 }  // extern "C"
+
+void qm_model_answer_exact(qmann_model *m, bool exact) { if (m) m->answer_exact = exact; }

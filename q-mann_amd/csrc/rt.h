@@ -6,6 +6,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <type_traits>
+#include "../../include/qmann_batch.h"
 
 // The batched entry points (qmann_*: they return QMANN_E* codes) do not end the host process on a HIP failure: inside a
 // QmBatched scope the failure is reported on stderr, remembered, and the entry point returns QMANN_EHIP.  The drop-in
@@ -48,26 +49,6 @@ static inline void qm_alloc(T **p, size_t n)
     // the reference never frees a null, so keep every slot non-null
     QM_HIP(hipMalloc((void **)p, (n ? n : 1) * sizeof(T)));
 }
-
-// Calls inside a QmAnswerExact scope take the serial-order float answer kernels (bit-equal to lib/layer_cuda.cu:70-80's loop):
-// the drop-in queue (abi_defer.hip), whose results are promised to be those of the verb-by-verb loop.
-inline thread_local int qm_answer_exact_depth = 0;
-struct QmAnswerExact {
-    QmAnswerExact() { ++qm_answer_exact_depth; }
-    ~QmAnswerExact() { --qm_answer_exact_depth; }
-    QmAnswerExact(const QmAnswerExact &) = delete;
-};
-
-// A hop-plane's size in rows, from a caller that knows it, for calls that pass hop_stride = 0 (tied hops: one plane for every
-// hop, qmann_model's hops_and_answer): hops_quad.h addresses rows by 32-bit byte offsets from the plane's start and must know that
-// the plane stays below 2 GiB; without the hint such a call keeps the one-wavefront-per-query kernel.
-inline thread_local size_t qm_rows_hint = 0;
-struct QmRowsHint {
-    size_t prev;
-    explicit QmRowsHint(size_t rows) : prev(qm_rows_hint) { qm_rows_hint = rows; }
-    ~QmRowsHint() { qm_rows_hint = prev; }
-    QmRowsHint(const QmRowsHint &) = delete;
-};
 
 // The library's A/B and tuning switches (INTEGRATION.md lists them) are read from the environment ONCE per process -- on
 // first use, through a thread-safe function-local static -- and then live in this struct: no launch calls getenv(), which
@@ -117,13 +98,28 @@ struct QmSide {
     // "side by side" and "in sequence" only -- never a result.
     volatile uint32_t *last_counts;
 };
-// A batch's two index lists (stories of <= 16 rows / longer ones: hops_quad.h::k_split_by_length) prepared AHEAD of the hop launch:
-// the host model computes them on the second stream while the stories are embedded and names them here for the next hop
-// launch of this thread, which takes them if (row_off, n_query, max_slots) are the ones it was asked for.
-struct QmSplitReady { const uint32_t *row_off; uint32_t n_query, max_slots; uint32_t *ws; };
-extern thread_local QmSplitReady qm_split_ready;
-bool qm_split_applies(size_t rows_total, uint32_t n_query, uint32_t max_slots);          // (batch_hops.hip)
+// What a caller inside the library knows about a hop call beyond the public arguments; the public qmann_hops_* pass an empty one.
+struct QmHopHints {
+    // The plane's size in rows for calls that pass hop_stride = 0 (tied hops: one plane for every hop); 0 = unknown.  hops_quad.h
+    // addresses rows by 32-bit byte offsets and must know that the plane stays below 2 GiB: without it such a call keeps the lean kernel.
+    size_t plane_rows = 0;
+    // The index lists of THIS call's (row_off, n_query, max_slots) from qm_split_early, made ahead of the launch; null = none
+    uint32_t *split_ws = nullptr;
+};
+// qmann_hops_i8 / qmann_hops_packed (include/qmann_batch.h) with the caller's hints         (batch_hops.hip, batch_hops_ham.hip)
+int qm_hops_i8(const qmann_net *net, const int8_t *keys, const int8_t *vals, size_t hop_stride, const uint32_t *row_off, uint32_t max_slots,
+               const float *u0, float *u_out, const qmann_taps *taps, uint32_t n_query, void *stream, const QmHopHints &hints);
+int qm_hops_packed(const qmann_net *net, const uint64_t *key_planes, size_t key_hop_stride, const int8_t *vals, size_t val_hop_stride, const uint32_t *row_off,
+                   uint32_t max_slots, const float *u0, float *u_out, const qmann_taps *taps, uint32_t n_query, void *stream, const QmHopHints &hints);
+// Will qm_hops_i8 on int8 planes of `plane_rows` rows split this batch by story length (hops_host.h::hop_form of the call)?  Then
+// the lists can be made early: [0] short count, [1] long count, the two lists (hops_quad.h::split_lists), in the scratch words of
+// stream `owner`, computed on `run_on`.
+bool qm_hops_will_split(const qmann_net *net, size_t plane_rows, uint32_t max_slots, uint32_t n_query);       // (batch_hops.hip)
 uint32_t *qm_split_early(const uint32_t *row_off, uint32_t n_query, uint32_t max_slots, hipStream_t owner, hipStream_t run_on);
+// qmann_model_forward_* of `m` keep the serial-order float answer kernels (bit-equal to lib/layer_cuda.cu:70-80's loop): set by the
+// drop-in queue (abi_defer.hip), whose results are promised to be those of the verb-by-verb loop.     (model_host.hip)
+struct qmann_model;
+void qm_model_answer_exact(qmann_model *m, bool exact);
 constexpr uint32_t kQmCorunMinQueries = 32768;        // batches below run their kernels in sequence (measured equal at 32 768 and 65 536 queries, +4 % at 262 000)
 QmSide *qm_side_stream(hipStream_t stream);       // (tuning.hip)
 

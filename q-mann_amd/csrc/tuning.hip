@@ -4,7 +4,6 @@
 #include <map>
 #include <mutex>
 #include <utility>
-#include "../../include/qmann_batch.h"
 
 namespace {
 
@@ -88,8 +87,6 @@ uint32_t *qm_scratch_u32(size_t words, hipStream_t stream)
     }
     return b.p;
 }
-
-thread_local QmSplitReady qm_split_ready{nullptr, 0, 0, nullptr};
 
 QmSide *qm_side_stream(hipStream_t stream)
 {
