@@ -150,7 +150,8 @@ int qmann_hops_i8(const qmann_net *net, const int8_t *keys, const int8_t *vals, 
  * One workgroup owns a tile of 1, 2, 4 or 8 queries and scans the plane once per hop for all of them (the plane stays in L2;
  * csrc/batch_hops_shared.hip); the library chooses the tile, QMANN_SHARED_QT (environment) forces one that fits.
  * attention_mode QMANN_ATT_FIXED only -- every qmann_net field qmann_hops_i8 honours in that mode is honoured; any other
- * attention mode returns QMANN_EUNSUPPORTED with nothing launched (the Hamming and float forms are follow-ups).
+ * attention mode returns QMANN_EUNSUPPORTED with nothing launched (Hamming V0 / V1 on packed codes: qmann_hops_shared_packed
+ * below; the APPX and float forms are follow-ups).
  * n_slots = 0: QMANN_EINVAL.  A memory too long for LDS with one query per workgroup: QMANN_ERANGE (sizing helper below).
  * One ordered step on `stream`, no second stream, no library scratch: it can be captured in a graph. */
 int qmann_hops_shared_i8(const qmann_net *net, const int8_t *keys, const int8_t *vals, size_t hop_stride,
@@ -172,6 +173,24 @@ int qmann_hops_packed(const qmann_net *net, const uint64_t *key_planes, size_t k
                       const int8_t *vals, size_t val_hop_stride, const uint32_t *row_off,
                       uint32_t max_slots, const float *u0, float *u_out, const qmann_taps *taps,
                       uint32_t n_query, void *stream);
+
+/* qmann_hops_packed when every query reads the SAME memory: key_planes uint64 [n_hop][n_slots][Dp/64][num_bit] (the layout of
+ * qmann_pack_bitplanes, 16-byte aligned, hop planes key_hop_stride bytes apart), vals int8 [n_hop][n_slots][Dp] sign-magnitude
+ * (val_hop_stride bytes apart); both strides 0 = one plane for every hop (tied).  The planes are packed once for all queries and
+ * held once -- qmann_hops_packed wants a private copy of keys AND values per query.
+ * Results equal qmann_hops_packed on n_query copies of the planes and values, bit for bit; every qmann_net field that call
+ * honours is honoured.  Taps as in qmann_hops_shared_i8: score_codes / scores / probs [n_hop][n_query][n_slots], o / u
+ * [n_query][n_hop][D]; allowed with stride 0.  One workgroup owns a tile of 1, 2, 4 or 8 queries and scans the planes once per
+ * hop for all of them (csrc/batch_hops_shared_ham.hip); the library chooses the tile, QMANN_SHARED_QT forces one that fits.
+ * Nothing is launched and the code returned is: QMANN_EUNSUPPORTED for an attention mode other than QMANN_ATT_HAMMING_V0 / _V1,
+ * num_bit outside {1, 2, 4, 8}, a single plane of 64 columns (a key row is half a 16-byte load), attention formats the Hamming
+ * family refuses (word length 7 with an integer bit is wanted); QMANN_EINVAL for null or misaligned pointers, n_slots = 0, a
+ * key_hop_stride that is not val_hop_stride / Dp rows of planes; QMANN_ERANGE for a memory too long for LDS with one query per
+ * workgroup (sizing helper below) and for 2^24 queries or more; QMANN_OK for n_query = 0.
+ * One ordered step on `stream`, no second stream, no library scratch: it can be captured in a graph. */
+int qmann_hops_shared_packed(const qmann_net *net, const uint64_t *key_planes, size_t key_hop_stride,
+                             const int8_t *vals, size_t val_hop_stride, uint32_t n_slots, const float *u0,
+                             float *u_out, const qmann_taps *taps, uint32_t n_query, void *stream);
 
 /* Answer layer for a batch: logits = W_ans . u (float, ds_ans is always float: MemN2N.c:902-906),
  * softmax over V, arg-max with ties to the highest index, and -- when `answer` is given -- the
@@ -265,6 +284,12 @@ size_t qmann_hops_shared_lds_bytes(uint32_t n_slots, uint32_t queries_per_group)
 /* queries per workgroup qmann_hops_shared_i8 would take for this call on the current device, QMANN_SHARED_QT included
  * (1, 2, 4 or 8; 0 where the call would launch nothing) -- for tests and timing tools that must know which tile ran */
 uint32_t qmann_hops_shared_tile(uint32_t n_slots, uint32_t n_query);
+
+/* the same two for qmann_hops_shared_packed, whose LDS depends on the net (V0 keeps tables of num_bit . dim_emb + 1 bins per
+ * query): bytes of one workgroup that owns `queries_per_group` queries (within 160 KiB - 1 KiB for one query, or the call
+ * returns QMANN_ERANGE), and the tile the call would take (0 where it would launch nothing) */
+size_t qmann_hops_shared_packed_lds_bytes(const qmann_net *net, uint32_t n_slots, uint32_t queries_per_group);
+uint32_t qmann_hops_shared_packed_tile(const qmann_net *net, uint32_t n_slots, uint32_t n_query);
 
 /* The library's A/B switches (environment variables QMANN_NO_LEAN, QMANN_NO_MID, QMANN_NO_W7, QMANN_NO_TIED, QMANN_NO_TIGHT,
  * QMANN_SHARED_QT, QMANN_LEAN_SPARSE, QMANN_EMBED_VALU, QMANN_EMBED_GENERAL_EPILOGUE, QMANN_ANSWER_TWO_PASS: INTEGRATION.md) are read ONCE,

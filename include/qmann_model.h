@@ -100,6 +100,31 @@ int qmann_model_forward_shared_words(qmann_model *m, const uint16_t *story_words
                                      const uint16_t *question_words, uint32_t max_q_words, uint32_t n_query,
                                      const uint32_t *answer, uint32_t *pred, float *cost, uint32_t *match, void *stream);
 
+/* Memorise once, ask many times: a knowledge base is embedded (and, for Hamming V0 / V1 models, packed into bit planes) ONCE
+ * and kept by the model; every later ask embeds only its questions and attends to the kept memory.
+ *
+ * qmann_model_memorize_words: story_words [n_rows][max_words] as above.  Embeds every hop's memory (one plane when the hops are
+ * tied) into buffers the model owns BESIDE its per-batch workspace -- qmann_model_forward_words / _bow / _shared_words calls in
+ * between do not disturb them -- and replaces an earlier memory.  Attention modes QMANN_ATT_FIXED (asks run qmann_hops_shared_i8)
+ * and QMANN_ATT_HAMMING_V0 / _V1 (packed planes, qmann_hops_shared_packed); QMANN_ATT_FLOAT and _APPX return
+ * QMANN_EUNSUPPORTED, and so does a Hamming model the packed call would refuse (num_bit outside {1, 2, 4, 8}; 64 padded columns
+ * with one bit).  n_rows = 0: QMANN_EINVAL.  A memory too long for LDS with one query per workgroup: QMANN_ERANGE, here, so that
+ * an ask cannot fail late.  A call that fails leaves the model with nothing memorised.
+ *
+ * qmann_model_ask_words: question_words [n_query][max_q_words]; answer, pred, cost, match as in qmann_model_forward_words;
+ * same results as qmann_model_forward_words on n_query copies of the memorised story; qmann_model_last_u holds the final state
+ * afterwards.  Nothing memorised: QMANN_EINVAL.  It allocates nothing once the question workspace has its size (one earlier ask
+ * of at least n_query questions), so it can be captured in a graph and replayed.
+ *
+ * All work of both calls goes to the caller's `stream` itself.  ORDERING IS THE CALLER'S: an ask on another stream than the
+ * memorize before it must be ordered behind it by the caller (an event, a synchronisation), and a memorize must not be issued
+ * while asks on the earlier memory are still running on other streams -- it frees or overwrites what they read.
+ * qmann_model_memory_rows: rows of the kept memory, 0 = nothing memorised. */
+int qmann_model_memorize_words(qmann_model *m, const uint16_t *story_words, uint32_t n_rows, uint32_t max_words, void *stream);
+int qmann_model_ask_words(qmann_model *m, const uint16_t *question_words, uint32_t max_q_words, uint32_t n_query,
+                          const uint32_t *answer, uint32_t *pred, float *cost, uint32_t *match, void *stream);
+uint32_t qmann_model_memory_rows(const qmann_model *m);
+
 /* Forward from the reference's float bag-of-words pools (dev_m_test / dev_q_test, MemN2N.c:2337-2349):
  *   story [rows_total][dim_input] float, question [n_query][dim_input] float. */
 int qmann_model_forward_bow(qmann_model *m, const float *story, uint32_t rows_total, const float *question,

@@ -27,10 +27,6 @@
 
 namespace {
 
-constexpr uint32_t kOffUb = kOffHist;                 // u8  [256]  sign-magnitude bytes of Q_att(u)   (reuses the
-constexpr uint32_t kOffUpl = kOffHist + 256;          // u64 [4][8] bit-planes of u                    histogram area)
-static_assert(kOffUpl % 8 == 0 && kOffUpl + 4 * 8 * 8 <= kOffPtab, "u planes must fit the histogram area");
-
 // LPRK: lanes per key row; DP: padded embedding width; MODE; NB: planes (packed modes)
 // (bounding the kernel to 96 VGPRs for a fifth workgroup per CU spills: 0.82 -> 0.65-0.70 of peak for V0, 0.75 -> 0.73-0.75 for APPX;
 // removing the histogram atomics changes nothing: the kernel is not bound by them)
@@ -273,17 +269,6 @@ k_pack_planes(const uint8_t *__restrict__ sm, uint64_t *__restrict__ planes, siz
             if (ok[r] && t + 4 < nb) planes[item * nb + t + 4] = mine[1];
         }
     }
-}
-
-// what the Hamming family asks of a hop besides (hops_host.h::fill_hop_args): attention word length 7 with an integer bit
-int check_ham_hop(const qmann_net *net, uint32_t h)
-{
-    return (net->att[h].iwl + net->att[h].frac != 7 || net->att[h].iwl < 1) ? QMANN_EUNSUPPORTED : QMANN_OK;
-}
-
-size_t ham_lds_bytes(uint32_t max_slots, uint32_t v0_bins)
-{
-    return (size_t)kOffScores + (((size_t)max_slots * 2 + 15) & ~(size_t)15) + (v0_bins ? v0_table_bytes(v0_bins) : 0);
 }
 
 // What every entry point of the family does between its own checks and its launch: HopArgs (the shared checks and fields, then

@@ -1,0 +1,278 @@
+// batch_hops_shared_ham.hip -- qmann_hops_shared_packed: the fused hops on PACKED BINARY CODES when every query reads the SAME
+// memory (one knowledge base or document, many questions).  It is to k_hops_ham (batch_hops_ham.hip) what k_hops_shared
+// (batch_hops_shared.hip) is to k_hops_fixed.
+//
+// The key planes are packed once for every query (qmann_pack_bitplanes) and are small: 320 KB per hop at 10 000 x 256 with one
+// bit, 2.56 MB with eight -- inside an XCD's 4 MiB L2.  One 256-thread workgroup owns QT queries and per hop
+//
+//   1. builds each query's attention operand exactly as k_hops_ham does (ham_ubyte, the ballots), on that query's LDS slice;
+//   2. scans the key planes ONCE for its tile of queries: a 16-byte load (plain, not `nt`: the plane is to stay in L2) is
+//      assembled into its two 64-bit words -- and for V1 the key's sign plane is fetched by the quad-permute moves -- once
+//      (ham_common.h::plane_key_split), then meets QT queries' plane words (plane_lane_sum_split: the integer operations of
+//      plane_lane_sum, so the scores are those of qmann_hops_packed bit for bit);
+//   3. runs the rest of the hop per query, one after the other, on that query's slice: int16 scores, the V0 histogram softmax or
+//      the per-slot softmax with its threshold shortcut (ham_common.h), survivor list, sparse read-out, linear map, hop update.
+//
+// Unlike the fixed-point form the tile saves little vector work -- a packed row costs a handful of operations per query --;
+// what it shares is one read of the plane from L2 and that load's latency.
+// A last tile with fewer than QT queries scans with a live query's constants in the spare places and drops their sums.
+#include "ham_common.h"
+#include "hops_host.h"
+
+namespace {
+
+constexpr size_t kSharedLdsLimit = 160 * 1024 - 1024;          // as qmann_hops_packed: a little static LDS is used besides
+
+// one query's slice of the workgroup's LDS (the carve-up of k_hops_ham: ham_common.h::ham_lds_bytes)
+struct HamQueryLds {
+    uint8_t *ub, *live_kp, *v0_kp;
+    uint64_t *upl;
+    float *u_f, *o_f, *v0_p;
+    short *ku;
+    uint32_t *live_row, *misc, *v0_hist;
+    double *red;
+    int16_t *sc;
+    __device__ __forceinline__ HamQueryLds(unsigned char *b, uint32_t lds_slots, uint32_t nbins)
+        : ub(b + kOffUb), live_kp(b + kOffLiveKp), upl((uint64_t *)(b + kOffUpl)), u_f((float *)(b + kOffU)), o_f((float *)(b + kOffO)),
+          ku((short *)(b + kOffKu)), live_row((uint32_t *)(b + kOffLiveRow)), misc((uint32_t *)(b + kOffMisc)),
+          red((double *)(b + kOffRed)), sc((int16_t *)(b + kOffScores))
+    {
+        unsigned char *tab = b + kOffScores + (((size_t)lds_slots * sizeof(int16_t) + 15) & ~(size_t)15);   // V0 tables behind the scores
+        v0_hist = (uint32_t *)tab;
+        v0_p = (float *)(tab + v0_hist_bytes(nbins));
+        v0_kp = tab + 2 * v0_hist_bytes(nbins);
+    }
+};
+
+// what a query brings to the scan: its plane words and sign planes at this lane's (group, plane) positions
+struct PlaneQuery { uint64_t u[2], us[2]; };
+
+// hops_common.h::scan_rows<LPR, UN, .., kWaves> for a tile of QT queries on one plane: the same tiles, the same two in flight, the
+// same clamped last tile; the key-only work is done once per loaded row.  retire(t, r, v): row r of query t has sum v.
+// Needs S >= one tile of rows.
+template <int LPR, int UN, int QT, int MODE, int NB, typename Retire>
+__device__ __forceinline__ void scan_planes_shared(const uint8_t *__restrict__ kb, uint32_t S, const PlaneQuery (&c)[QT],
+                                                   const uint64_t (&valid)[2], const int (&wgt)[2], uint32_t nq, Retire retire,
+                                                   uint32_t lane, uint32_t wave)
+{
+    constexpr uint32_t RPW = kWave / LPR, TILE = RPW * UN, RowBytes = LPR * 16, STEP = kWaves * TILE;
+    const uint32_t sub = lane / LPR, chunk = lane % LPR;
+    const uint32_t n_tiles = (S + TILE - 1) / TILE;
+    const uint8_t *lane_base = kb + chunk * 16;
+    auto tile_start = [&](uint32_t base) { return base + TILE <= S ? base : S - TILE; };
+    auto issue = [&](i32x4 (&x)[UN], uint32_t base) {
+        const uint8_t *p = lane_base + (size_t)(tile_start(base) + sub) * RowBytes;
+#pragma unroll
+        for (int j = 0; j < UN; j++) x[j] = load16<false>(p + (size_t)j * RPW * RowBytes);
+    };
+    auto reduce = [&](const i32x4 (&x)[UN], uint32_t base) {
+        int s[QT][UN];
+#pragma unroll
+        for (int j = 0; j < UN; j++) {
+            uint64_t k[2], ks;
+            plane_key_split<MODE, NB>(x[j], k, ks);                // key-only work: once per tile of queries
+#pragma unroll
+            for (int t = 0; t < QT; t++) s[t][j] = row_lanes_sum<LPR>(plane_lane_sum_split<MODE, NB>(k, ks, c[t].u, c[t].us, valid, wgt));
+        }
+        const uint32_t start = tile_start(base);
+#pragma unroll
+        for (int t = 0; t < QT; t++) {
+            if ((uint32_t)t >= nq) break;                          // (workgroup-uniform)
+#pragma unroll
+            for (int j0 = 0; j0 < UN; j0 += LPR) {                 // lane (sub, chunk) retires row j0 + chunk, as scan_rows does
+                int v = s[t][j0];
+#pragma unroll
+                for (int i = 1; i < LPR && j0 + i < UN; i++) v = (chunk == (uint32_t)i) ? s[t][j0 + i] : v;
+                const uint32_t j = j0 + chunk;
+                const uint32_t r = start + j * RPW + sub;
+                if (j < (uint32_t)UN && r >= base) retire((uint32_t)t, r, v);
+            }
+        }
+    };
+
+    if (wave >= n_tiles) return;
+    i32x4 xa[UN], xb[UN];
+    uint32_t base = wave * TILE;
+    issue(xa, base);
+    for (uint32_t t = wave; t < n_tiles; t += 2 * kWaves) {
+        issue(xb, base + STEP);
+        reduce(xa, base);
+        if (t + kWaves >= n_tiles) break;
+        issue(xa, base + 2 * STEP);
+        reduce(xb, base + STEP);
+        base += 2 * STEP;
+    }
+}
+
+// LPRK: lanes per key row (16 LPRK bytes); DP: padded embedding width; MODE: kModeV0 / kModeV1; NB: planes; QT: queries per
+// workgroup.  per_q: bytes of LDS per query (ham_lds_bytes); a.max_slots = n_slots >= 1
+template <int LPRK, int DP, int MODE, int NB, int QT>
+__global__ void __launch_bounds__(kBlock, 1)
+k_hops_shared_ham(const HopArgs a, const uint32_t n_query, const uint32_t per_q)
+{
+    static_assert(mode_is_planes(MODE), "packed planes only");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr uint32_t UN = kUnrollDefault;
+    const uint32_t tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+    const uint32_t q0 = blockIdx.x * QT;
+    const uint32_t nq = n_query - q0 < (uint32_t)QT ? n_query - q0 : (uint32_t)QT;     // queries of this tile (the last may be short)
+    const uint32_t S = a.max_slots, D = a.D;
+    const uint32_t nbins = NB * D + 1;
+    auto slice = [&](uint32_t t) { return HamQueryLds(smem + t * per_q, S, nbins); };
+
+    for (uint32_t t = 0; t < nq; t++) slice(t).u_f[tid] = (tid < D) ? a.u0[(size_t)(q0 + t) * D + tid] : 0.0f;
+    __syncthreads();
+
+    for (uint32_t h = 0; h < a.n_hop; h++) {
+        const QFmt fm = a.att[h], fb = a.bin;
+        // per query: codes of u (Q_bin for the linear map), sign-magnitude Q_att bytes and their planes for the attention
+        for (uint32_t t = 0; t < nq; t++) {
+            const HamQueryLds L = slice(t);
+            const float uv = L.u_f[tid];
+            L.ku[tid] = (short)((tid < D) ? qm_code_or_sign(uv, fb.iwl, fb.frac) : 0);
+            const float ua = relu_if(uv, hop_relu(a, h));                    // what the attention reads
+            const uint32_t ubyte = ham_ubyte(ua, fm, tid < D);
+            L.ub[tid] = (uint8_t)ubyte;
+#pragma unroll
+            for (int i = 0; i < NB; i++) {
+                const uint64_t word = __ballot((ubyte >> (7 - i)) & 1u);
+                if (lane == 0) L.upl[wave * 8 + i] = word;         // wavefront w covers columns 64w .. 64w+63
+            }
+            if (tid == 0) L.misc[0] = 0u;
+            if (mode_is_v0(MODE))
+                for (uint32_t d = tid; d < nbins; d += kBlock) L.v0_hist[d] = 0u;
+        }
+        __syncthreads();
+
+        // the scan: one pass over the key planes for the whole tile
+        const float scale = MODE == kModeV1 ? qm_scale_down(1.0f, NB) : 1.0f;
+        const uint8_t *kb = (const uint8_t *)a.keys + (size_t)h * a.key_hop_stride;
+        auto retire = [&](uint32_t t, uint32_t r, int v) {
+            const HamQueryLds L = slice(t);
+            L.sc[r] = (int16_t)v;
+            if (mode_is_v0(MODE)) atomicAdd(&L.v0_hist[v], 1u);
+        };
+        if (S < (kWave / LPRK) * UN) {                               // below one tile of rows: right, not fast
+            for (uint32_t t = 0; t < nq; t++) {
+                PlaneConst c;
+                make_plane_const<NB>(c, slice(t).upl, lane % LPRK, D);
+                scan_rows_short<LPRK>(kb, S, [&](const i32x4 x) { return plane_lane_sum<MODE, NB>(x, c); },
+                                      [&](uint32_t r, int v) { retire(t, r, v); }, lane, wave, (uint32_t)kWaves);
+            }
+        } else {
+            PlaneQuery c[QT];
+            uint64_t valid[2];
+            int wgt[2];
+#pragma unroll
+            for (int t = 0; t < QT; t++) {
+                PlaneConst pc;                                       // spare places: a live query's constants
+                make_plane_const<NB>(pc, slice((uint32_t)t < nq ? (uint32_t)t : nq - 1).upl, lane % LPRK, D);
+                c[t].u[0] = pc.u[0]; c[t].u[1] = pc.u[1]; c[t].us[0] = pc.us[0]; c[t].us[1] = pc.us[1];
+                if (t == 0) { valid[0] = pc.valid[0]; valid[1] = pc.valid[1]; wgt[0] = pc.wgt[0]; wgt[1] = pc.wgt[1]; }   // (the lane's alone)
+            }
+            scan_planes_shared<LPRK, (int)UN, QT, MODE, NB>(kb, S, c, valid, wgt, nq, retire, lane, wave);
+        }
+        __syncthreads();
+
+        // the rest of the hop, query by query
+        for (uint32_t t = 0; t < nq; t++) {
+            const HamQueryLds L = slice(t);
+            const size_t tap_base = ((size_t)h * n_query + q0 + t) * S;
+            const uint32_t n_live = mode_is_v0(MODE)
+                ? ham_hist_softmax_survivors(a, h, S, nbins, tap_base, L.sc, L.v0_hist, L.v0_p, L.v0_kp, L.live_row, L.live_kp, L.misc, L.red, tid, lane, wave)
+                : ham_slot_softmax_survivors(a, h, S, scale, tap_base, L.sc, L.live_row, L.live_kp, L.misc, L.red, tid, lane, wave);
+            auto kp_of_row = [&](uint32_t r) { return mode_is_v0(MODE) ? (int)L.v0_kp[L.sc[r]] : (int)L.sc[r]; };
+            finish_hop<DP>(a, q0 + t, h, 0u, S, n_live, L.live_row, L.live_kp, kp_of_row, L.ku, L.u_f, L.o_f, tid);
+        }
+    }
+    for (uint32_t t = 0; t < nq; t++)
+        if (tid < D) a.u_out[(size_t)(q0 + t) * D + tid] = relu_if(slice(t).u_f[tid], a.en_non_lin != 0);
+}
+
+uint32_t v0_bins_of(const qmann_net *net)
+{
+    return net->attention_mode == QMANN_ATT_HAMMING_V0 ? net->num_bit * net->dim_emb + 1u : 0u;       // (the only mode with a table of bins)
+}
+
+// Queries per workgroup.  What LDS allows is the frame (about 31 KB per query at 10 000 slots with the V0 tables: 4 fit a CU's
+// 160 KiB, 8 do not); QMANN_SHARED_QT (1, 2, 4, 8) forces a tile that fits; a batch too small to give every CU a workgroup takes
+// smaller tiles.  Inside that frame: 4.  NOT MEASURED -- no timing of this kernel exists yet (tools/shared_ham_ab.py is the
+// tool; DESIGN.md section 5, "Measured, shared plane, Hamming" says what was and was not run).  The choice is by reasoning from the code: the
+// tile shares one L2 read of the plane and its latency among its queries, and 4 is the largest tile that fits at 10 000 slots.
+uint32_t choose_qt_ham(size_t per_q, uint32_t n_query)
+{
+    uint32_t fit = 8;
+    while (fit > 1 && fit * per_q > kSharedLdsLimit) fit >>= 1;
+    const uint32_t forced = qm_tuning().shared_qt;
+    if (forced) return forced < fit ? forced : fit;
+    uint32_t qt = fit < 4u ? fit : 4u;
+    while (qt > 1 && n_query / qt < qm_cu_count()) qt >>= 1;
+    return qt;
+}
+
+bool packed_form_ok(const qmann_net *net)
+{
+    if (net->attention_mode != QMANN_ATT_HAMMING_V0 && net->attention_mode != QMANN_ATT_HAMMING_V1) return false;
+    const uint32_t nb = net->num_bit;
+    return nb == 1 || nb == 2 || nb == 4 || nb == 8;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t qmann_hops_shared_packed_lds_bytes(const qmann_net *net, uint32_t n_slots, uint32_t queries_per_group)
+{
+    if (!net) return 0;
+    return (size_t)queries_per_group * ham_lds_bytes(n_slots, v0_bins_of(net));
+}
+
+uint32_t qmann_hops_shared_packed_tile(const qmann_net *net, uint32_t n_slots, uint32_t n_query)
+{
+    if (!net || !packed_form_ok(net) || n_slots == 0 || n_query == 0) return 0;
+    const size_t per_q = ham_lds_bytes(n_slots, v0_bins_of(net));
+    if (per_q > kSharedLdsLimit) return 0;
+    return choose_qt_ham(per_q, n_query);
+}
+
+int qmann_hops_shared_packed(const qmann_net *net, const uint64_t *key_planes, size_t key_hop_stride, const int8_t *vals,
+                             size_t val_hop_stride, uint32_t n_slots, const float *u0, float *u_out, const qmann_taps *taps,
+                             uint32_t n_query, void *stream)
+{
+    QmBatched qm_scope;
+    static const uint32_t no_row_off = 0;                     // this call has no row_off: the shared checks want a non-null one
+    if (const int rc = check_hop_call(net, key_planes, vals, &no_row_off, u0, u_out)) return rc;
+    if (!packed_form_ok(net)) return QMANN_EUNSUPPORTED;
+    const uint32_t nb = net->num_bit, Dp = net->dim_emb_pad;
+    if (key_hop_stride != val_hop_stride / Dp * (Dp / 64) * nb * 8) return QMANN_EINVAL;
+    if ((uintptr_t)key_planes & 15u) return QMANN_EINVAL;     // 16-byte loads
+    HopArgs a;
+    if (const int rc = fill_hop_args(a, net, key_planes, vals, key_hop_stride, val_hop_stride, &no_row_off, u0, u_out, taps, 0, check_ham_hop)) return rc;
+    if (n_slots == 0) return QMANN_EINVAL;
+    a.row_off = nullptr;
+    a.max_slots = a.rows_total = n_slots;
+    const size_t per_q = ham_lds_bytes(n_slots, v0_bins_of(net));
+    if (per_q > kSharedLdsLimit) return QMANN_ERANGE;
+    if (Dp / 64 * nb * 8 < 16) return QMANN_EUNSUPPORTED;     // Dp = 64 with a single plane: a key row is half a 16-byte load
+    if (n_query == 0) return QMANN_OK;
+    if (qm_too_many_queries(n_query)) return QMANN_ERANGE;
+
+    const bool v1 = net->attention_mode == QMANN_ATT_HAMMING_V1;
+    const uint32_t qt = choose_qt_ham(per_q, n_query);
+    hipStream_t st = (hipStream_t)stream;
+    qm_dispatch<64, 128, 256>(Dp, [&](auto dp) {
+        qm_dispatch<1, 2, 4, 8>(nb, [&](auto n) {
+            qm_dispatch<1, 2, 4, 8>(qt, [&](auto t) {
+                constexpr int DP = decltype(dp)::value, NB = decltype(n)::value, QT = decltype(t)::value, LPRK = (DP / 64) * NB * 8 / 16;
+                if constexpr (LPRK >= 1) {                      // (no instantiation for the case refused above)
+                    if (v1) qm_launch(k_hops_shared_ham<LPRK, DP, kModeV1, NB, QT>, qm_cdiv(n_query, qt), dim3(kBlock), (size_t)qt * per_q, st, a, n_query, (uint32_t)per_q);
+                    else qm_launch(k_hops_shared_ham<LPRK, DP, kModeV0, NB, QT>, qm_cdiv(n_query, qt), dim3(kBlock), (size_t)qt * per_q, st, a, n_query, (uint32_t)per_q);
+                }
+            });
+        });
+    });
+    QM_LAUNCH_CHECK();
+    return qm_scope.rc();
+}
+
+}  // extern "C"

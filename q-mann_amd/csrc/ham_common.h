@@ -22,6 +22,22 @@ constexpr bool mode_is_planes(int m) { return m == kModeV0 || m == kModeV1; }
 __host__ __device__ inline uint32_t v0_hist_bytes(uint32_t nbins) { return ((nbins * 4 + 15) / 16) * 16; }
 __host__ __device__ inline uint32_t v0_table_bytes(uint32_t nbins) { return 2 * v0_hist_bytes(nbins) + ((nbins + 15) / 16) * 16; }
 
+// LDS of the streaming kernels of the family (batch_hops_ham.hip, batch_hops_shared_ham.hip): hops_common.h's carve-up with the
+// attention operand in the histogram area, int16 scores, and the V0 tables behind them
+constexpr uint32_t kOffUb = kOffHist;                 // u8  [256]  sign-magnitude bytes of Q_att(u)   (reuses the
+constexpr uint32_t kOffUpl = kOffHist + 256;          // u64 [4][8] bit-planes of u                    histogram area)
+static_assert(kOffUpl % 8 == 0 && kOffUpl + 4 * 8 * 8 <= kOffPtab, "u planes must fit the histogram area");
+inline size_t ham_lds_bytes(uint32_t max_slots, uint32_t v0_bins)
+{
+    return (size_t)kOffScores + (((size_t)max_slots * 2 + 15) & ~(size_t)15) + (v0_bins ? v0_table_bytes(v0_bins) : 0);
+}
+
+// what the Hamming family asks of a hop besides (hops_host.h::fill_hop_args): attention word length 7 with an integer bit
+inline int check_ham_hop(const qmann_net *net, uint32_t h)
+{
+    return (net->att[h].iwl + net->att[h].frac != 7 || net->att[h].iwl < 1) ? QMANN_EUNSUPPORTED : QMANN_OK;
+}
+
 // ---- APPX: 4 key bytes against 4 query bytes -------------------------------------------------
 struct AppxConst {
     uint32_t um[4];   // |u| bytes
@@ -234,6 +250,151 @@ __device__ __forceinline__ void make_plane_const(PlaneConst &c, const uint64_t *
         c.valid[t] = ncol >= 64 ? ~0ull : ((1ull << ncol) - 1ull);
         c.wgt[t] = pl == 0 ? 0 : (1 << (NB - 1 - pl));
     }
+}
+
+// ---- plane_lane_sum split for a tile of queries on ONE plane (batch_hops_shared_ham.hip) ------------------------------------
+// The key half: the two 64-bit words of a loaded row and, for V1, the key's sign plane of the word's group (the quad-permute
+// fetch of plane_lane_sum) -- once per loaded row.
+template <int MODE, int NB>
+__device__ __forceinline__ void plane_key_split(const i32x4 x, uint64_t (&k)[2], uint64_t &ks)
+{
+    k[0] = (uint64_t)(uint32_t)x[0] | ((uint64_t)(uint32_t)x[1] << 32);
+    k[1] = (uint64_t)(uint32_t)x[2] | ((uint64_t)(uint32_t)x[3] << 32);
+    ks = k[0];                                          // (NB <= 2: this lane holds its group's sign plane)
+    if (MODE == kModeV1 && NB >= 4) {
+        constexpr int ctrl = (NB == 4) ? 0xA0 /* quad_perm [0,0,2,2] */ : 0x00 /* [0,0,0,0] */;
+        const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, x[0], ctrl, 0xF, 0xF, true);
+        const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, x[1], ctrl, 0xF, 0xF, true);
+        ks = (uint64_t)lo | ((uint64_t)hi << 32);
+    }
+}
+// The query half: one query's plane words `u` and sign planes `us` against the split key; `valid` and `wgt` depend on the lane
+// alone (one copy for the tile).  The integer operations of plane_lane_sum, term by term.
+template <int MODE, int NB>
+__device__ __forceinline__ int plane_lane_sum_split(const uint64_t (&k)[2], uint64_t ks, const uint64_t (&u)[2], const uint64_t (&us)[2],
+                                                    const uint64_t (&valid)[2], const int (&wgt)[2])
+{
+    if (MODE == kModeV0) return __popcll(~(k[0] ^ u[0]) & valid[0]) + __popcll(~(k[1] ^ u[1]) & valid[1]);
+    if (NB == 1) return 0;                              // no magnitude planes: every weight is zero
+    int acc = 0;
+#pragma unroll
+    for (int t = 0; t < 2; t++) {
+        const uint64_t eq = ~(k[t] ^ u[t]);
+        const uint64_t sdiff = (ks ^ us[t]) & valid[t];
+        const uint64_t ssame = ~(ks ^ us[t]) & valid[t];
+        acc += wgt[t] * (__popcll(eq & ssame) - __popcll(eq & sdiff));
+    }
+    return acc;
+}
+
+// ---- the softmax stages of the streaming kernels, per query ------------------------------------------------------------------
+// (COPIES of the two stages k_hops_ham carries inline, batch_hops_ham.hip, with the same thread-to-slot mapping and the same
+// float and double operations in the same order -- that kernel keeps its inline text so that its device assembly stays what was
+// measured (tools/device_asm_equal.sh), as hist_softmax_survivors does for k_hops_fixed; keep them in step.)
+// Both are called by the whole 256-thread workgroup after a barrier behind the scan, with misc[0] = 0 and S > 0 int16 scores in
+// `sc`; taps are written from index `tap_base` on; both end with a barrier and return the number of rows whose quantised weight
+// is non-zero (listed in live_row / live_kp up to kLiveCap).
+
+// V0: one exp per distinct count through the histogram `v0_hist` (nbins bins, filled by the scan); v0_p / v0_kp: p and Q(p)
+// per count afterwards
+__device__ __forceinline__ uint32_t ham_hist_softmax_survivors(const HopArgs &a, uint32_t h, uint32_t S, uint32_t nbins, size_t tap_base,
+                                                               const int16_t *sc, const uint32_t *v0_hist, float *v0_p, uint8_t *v0_kp,
+                                                               uint32_t *live_row, uint8_t *live_kp, uint32_t *misc, double *red,
+                                                               uint32_t tid, uint32_t lane, uint32_t wave)
+{
+    const QFmt fa = a.act[h];
+    // one exp per distinct count; normaliser sum_d count[d] . e[d] in double (lib/layer_cuda.cu:2024-2042)
+    const SmCfg smc = sm_cfg(a, h);
+    float xmax = -INFINITY;
+    for (uint32_t d = tid; d < nbins; d += kBlock)
+        if (v0_hist[d]) xmax = fmaxf(xmax, sm_scaled((float)d, smc));
+    xmax = block_max<float>(xmax, (float *)red, lane, wave);
+    double part = 0.0;
+    for (uint32_t d = tid; d < nbins; d += kBlock) {
+        const float e = sm_exp(sm_scaled((float)d, smc) - xmax, smc);
+        v0_p[d] = e;
+        if (v0_hist[d]) part += (double)v0_hist[d] * (double)e;
+    }
+    const double total = smc.base == QMANN_SOFTMAX_EXP ? block_sum_double(part, red, lane, wave)
+                                                       : block_serial_total_f32(S, lane, wave, red, [&](uint32_t r) { return v0_p[sc[r]]; });
+    for (uint32_t d = tid; d < nbins; d += kBlock) {
+        const float p = v0_hist[d] ? sm_quot(v0_p[d], total, smc) : 0.0f;
+        v0_p[d] = p;
+        v0_kp[d] = (uint8_t)qm_code(p, fa.iwl, fa.frac);
+    }
+    __syncthreads();
+    if (a.tap_codes || a.tap_scores || a.tap_probs) {
+        for (uint32_t r = tid; r < S; r += kBlock) {
+            const int v = sc[r];
+            if (a.tap_codes) a.tap_codes[tap_base + r] = v;
+            if (a.tap_scores) a.tap_scores[tap_base + r] = (float)v;
+            if (a.tap_probs) a.tap_probs[tap_base + r] = v0_p[v];
+        }
+    }
+    // rows whose quantised weight is non-zero: 8 scores per LDS read, their 8 table look-ups in flight together
+    for (uint32_t rb = tid * 8; rb < S; rb += kBlock * 8) {
+        const i32x4 v = *(const i32x4 *)(sc + rb);               // (the score array is padded to 8 rows)
+        uint8_t kp[8];
+#pragma unroll
+        for (int i = 0; i < 8; i++) kp[i] = v0_kp[rb + i < S ? ((uint32_t)v[i / 2] >> (16 * (i % 2))) & 0xFFFFu : 0u];
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            if (rb + i < S && kp[i]) {
+                const uint32_t n = atomicAdd(&misc[0], 1u);
+                if (n < (uint32_t)kLiveCap) { live_row[n] = rb + i; live_kp[n] = kp[i]; }
+            }
+        }
+    }
+    __syncthreads();
+    return misc[0];
+}
+
+// Every other mode: per slot (max, sum of exp in double, quotient) with the threshold / code_lo shortcut of k_hops_ham (its
+// comments hold the reasoning); `scale`: the unit of a score.  When the survivor list overflows, sc holds Q(p) per row afterwards.
+__device__ __forceinline__ uint32_t ham_slot_softmax_survivors(const HopArgs &a, uint32_t h, uint32_t S, float scale, size_t tap_base,
+                                                               int16_t *sc, uint32_t *live_row, uint8_t *live_kp, uint32_t *misc,
+                                                               double *red, uint32_t tid, uint32_t lane, uint32_t wave)
+{
+    const QFmt fa = a.act[h];
+    const SmCfg smc = sm_cfg(a, h);
+    // (float)score . scale is exact (integers below 2^24 times a power of two)
+    auto slot_x = [&](uint32_t r) { return sm_scaled((float)sc[r] * scale, smc); };
+    float xmax = -INFINITY;
+    for (uint32_t r = tid; r < S; r += kBlock) xmax = fmaxf(xmax, slot_x(r));
+    xmax = block_max<float>(xmax, (float *)red, lane, wave);
+    double part = 0.0;
+    for (uint32_t r = tid; r < S; r += kBlock) part += (double)sm_exp(slot_x(r) - xmax, smc);
+    const double total = smc.base == QMANN_SOFTMAX_EXP ? block_sum_double(part, red, lane, wave)
+                                                       : block_serial_total_f32(S, lane, wave, red, [&](uint32_t r) { return sm_exp(slot_x(r) - xmax, smc); });
+    const bool every = a.tap_codes || a.tap_scores || a.tap_probs || smc.shift;
+    const float thr = every ? 0.0f : (float)(total * (double)qm_scale_down(1.0f, fa.frac) * (1.0 - 9.5367431640625e-07));
+    int code_lo = INT_MIN;
+    if (!every && smc.base == QMANN_SOFTMAX_EXP && !smc.en_scale)
+        code_lo = (int)floorf((logf(thr) - 1e-3f + xmax) / scale) - 1;
+    for (uint32_t r = tid; r < S; r += kBlock) {
+        if ((int)sc[r] < code_lo) continue;
+        const float e = sm_exp(slot_x(r) - xmax, smc);
+        if (!(e >= thr)) continue;
+        const float p = sm_quot(e, total, smc);
+        if (a.tap_codes) a.tap_codes[tap_base + r] = sc[r];
+        if (a.tap_scores) a.tap_scores[tap_base + r] = (float)sc[r] * scale;
+        if (a.tap_probs) a.tap_probs[tap_base + r] = p;
+        const int kp = qm_code(p, fa.iwl, fa.frac);
+        if (kp) {
+            const uint32_t i = atomicAdd(&misc[0], 1u);
+            if (i < (uint32_t)kLiveCap) { live_row[i] = r; live_kp[i] = (uint8_t)kp; }
+        }
+    }
+    __syncthreads();
+    const uint32_t n_live = misc[0];
+    if (n_live > (uint32_t)kLiveCap) {                  // keep the overflow path exact: park Q(p) in sc
+        for (uint32_t r = tid; r < S; r += kBlock) {
+            const float p = sm_quot(sm_exp(slot_x(r) - xmax, smc), total, smc);
+            sc[r] = (int16_t)qm_code(p, fa.iwl, fa.frac);
+        }
+        __syncthreads();
+    }
+    return n_live;
 }
 
 }  // namespace

@@ -91,6 +91,13 @@ struct qmann_model {
     uint16_t *bow_words = nullptr;
     uint32_t *bow_irr = nullptr;
     size_t cap_rows = 0, cap_plane_words = 0, cap_query = 0, cap_bow = 0;
+    // the memorised knowledge base (qmann_model_memorize_words): its own buffers beside the per-batch workspace above, which the
+    // forward calls regrow and overwrite.  int8 memories of every hop (one plane when tied); for V0 / V1 models the packed key
+    // planes as well -- the asks then read mem_planes and mem_vals.  mem_rows = 0: nothing memorised
+    int8_t *mem_keys = nullptr, *mem_vals = nullptr;
+    uint64_t *mem_planes = nullptr;
+    uint32_t mem_rows = 0;
+    size_t mem_cap_rows = 0;
     bool answer_exact = false;   // rt.h::qm_model_answer_exact: the float answer layer keeps the serial order of additions
 };
 
@@ -194,6 +201,19 @@ bool use_planes(const qmann_model *m, uint32_t max_slots)
     return packed_mode(m->net) && m->net.num_bit < 8 && max_slots > 64 && (m->Dp / 64) * m->net.num_bit * 8 >= 16 && m->tied && m->H > 1;
 }
 
+// the question side of the workspace: u0 and u of n_query queries
+int ensure_queries(qmann_model *m, uint32_t n_query)
+{
+    if (n_query > m->cap_query || !m->u0 || !m->u) {
+        const size_t cap = (size_t)n_query + n_query / 4;
+        m->cap_query = 0;
+        const bool ok_0 = regrow(&m->u0, cap * m->D), ok_u = regrow(&m->u, cap * m->D);
+        if (!ok_0 || !ok_u) return QMANN_EHIP;
+        m->cap_query = cap;
+    }
+    return QMANN_OK;
+}
+
 int ensure(qmann_model *m, size_t rows, uint32_t n_query, bool planes)
 {
     // A capacity is recorded only when every buffer it describes exists: after a failed allocation the next call tries again
@@ -214,14 +234,7 @@ int ensure(qmann_model *m, size_t rows, uint32_t n_query, bool planes)
             m->cap_plane_words = words;
         }
     }
-    if (n_query > m->cap_query || !m->u0 || !m->u) {
-        const size_t cap = (size_t)n_query + n_query / 4;
-        m->cap_query = 0;
-        const bool ok_0 = regrow(&m->u0, cap * m->D), ok_u = regrow(&m->u, cap * m->D);
-        if (!ok_0 || !ok_u) return QMANN_EHIP;
-        m->cap_query = cap;
-    }
-    return QMANN_OK;
+    return ensure_queries(m, n_query);
 }
 
 // the float matrices of the float embedding kernels: the tables' grid values (qmann_dequantize_table_f32)
@@ -426,6 +439,7 @@ void qmann_model_destroy(qmann_model *m)
     DeviceScope on(m->device);
     auto drop = [](void *p) { if (p) QM_HIP(hipFree(p)); };
     drop(m->blob); drop(m->w_q);             // (w_a / w_c point into w_q's allocation)
+    drop(m->mem_keys); drop(m->mem_vals); drop(m->mem_planes);
     drop(m->keys); drop(m->vals); drop(m->planes); drop(m->u0); drop(m->u); drop(m->bow_words); drop(m->bow_irr);
     delete m;
 }
@@ -492,6 +506,72 @@ int qmann_model_forward_shared_words(qmann_model *m, const uint16_t *story_words
     rc = qmann_answer_f32(&m->net, m->w_ans, m->u, answer, pred, nullptr, cost, match, n_query, stream);
     return rc ? rc : qm_scope.rc();
 }
+
+int qmann_model_memorize_words(qmann_model *m, const uint16_t *story_words, uint32_t n_rows, uint32_t max_words, void *stream)
+{
+    QmBatched qm_scope;
+    if (!m) return QMANN_EINVAL;
+    const qmann_net &n = m->net;
+    const bool packed = packed_mode(n);
+    if (!packed && n.attention_mode != QMANN_ATT_FIXED) return QMANN_EUNSUPPORTED;      // (what the shared-plane hop calls cover)
+    if (packed) {                                            // what qmann_hops_shared_packed would refuse, said here
+        const uint32_t nb = n.num_bit;
+        if ((nb != 1 && nb != 2 && nb != 4 && nb != 8) || (m->Dp / 64) * nb * 8 < 16) return QMANN_EUNSUPPORTED;
+        for (uint32_t h = 0; h < m->H; h++)
+            if (n.att[h].iwl + n.att[h].frac != 7 || n.att[h].iwl < 1) return QMANN_EUNSUPPORTED;
+    }
+    if (!story_words || n_rows == 0) return QMANN_EINVAL;
+    // the memory's length against LDS now, so that an ask cannot fail late
+    const size_t lds = packed ? qmann_hops_shared_packed_lds_bytes(&n, n_rows, 1) : qmann_hops_shared_lds_bytes(n_rows, 1);
+    if (lds > 160 * 1024 - 1024) return QMANN_ERANGE;
+    DeviceScope on(m->device);
+    m->mem_rows = 0;                                         // (a failure below leaves nothing memorised)
+    const size_t n_plane = m->tied ? 1 : m->H;
+    if (n_rows > m->mem_cap_rows || !m->mem_keys || !m->mem_vals || (packed && !m->mem_planes)) {
+        const size_t cap = n_rows;
+        m->mem_cap_rows = 0;
+        const bool ok_k = regrow(&m->mem_keys, n_plane * cap * m->Dp), ok_v = regrow(&m->mem_vals, n_plane * cap * m->Dp);
+        const bool ok_p = !packed || regrow(&m->mem_planes, n_plane * cap * (m->Dp / 64) * n.num_bit);
+        if (!ok_k || !ok_v || !ok_p) return QMANN_EHIP;
+        m->mem_cap_rows = cap;
+    }
+    const size_t plane = (size_t)n_rows * m->Dp;
+    int rc = qmann_embed_story_idx(&m->emb_net, story_words, n_rows, max_words, 1, m->t_a, m->t_c, m->mem_keys, m->mem_vals, plane, stream);
+    if (rc) return rc;
+    if (packed) {
+        rc = qmann_pack_bitplanes(m->mem_keys, m->mem_planes, n_plane * n_rows, m->Dp, n.num_bit, stream);
+        if (rc) return rc;
+    }
+    if (qm_scope.rc()) return qm_scope.rc();
+    m->mem_rows = n_rows;
+    return QMANN_OK;
+}
+
+int qmann_model_ask_words(qmann_model *m, const uint16_t *question_words, uint32_t max_q_words, uint32_t n_query,
+                          const uint32_t *answer, uint32_t *pred, float *cost, uint32_t *match, void *stream)
+{
+    QmBatched qm_scope;
+    if (!m || m->mem_rows == 0) return QMANN_EINVAL;
+    if (n_query == 0) return QMANN_OK;
+    if (!question_words || !pred) return QMANN_EINVAL;
+    DeviceScope on(m->device);
+    int rc = ensure_queries(m, n_query);
+    if (rc) return rc;
+    const uint32_t S = m->mem_rows;
+    const size_t plane = m->tied ? 0 : (size_t)S * m->Dp;
+    rc = qmann_embed_query_idx(&m->net, question_words, max_q_words, m->t_q, m->u0, n_query, stream);
+    if (rc) return rc;
+    if (packed_mode(m->net))
+        rc = qmann_hops_shared_packed(&m->net, m->mem_planes, plane / m->Dp * (m->Dp / 64) * m->net.num_bit * 8, m->mem_vals, plane, S,
+                                      m->u0, m->u, nullptr, n_query, stream);
+    else
+        rc = qmann_hops_shared_i8(&m->net, m->mem_keys, m->mem_vals, plane, S, m->u0, m->u, nullptr, n_query, stream);
+    if (rc) return rc;
+    rc = (m->answer_exact ? qmann_answer_f32_serial : qmann_answer_f32)(&m->net, m->w_ans, m->u, answer, pred, nullptr, cost, match, n_query, stream);
+    return rc ? rc : qm_scope.rc();
+}
+
+uint32_t qmann_model_memory_rows(const qmann_model *m) { return m ? m->mem_rows : 0u; }
 
 int qmann_model_forward_bow(qmann_model *m, const float *story, uint32_t rows_total, const float *question,
                             const uint32_t *row_off, uint32_t max_slots, uint32_t n_query, const uint32_t *answer,

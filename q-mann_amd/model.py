@@ -316,6 +316,34 @@ class QNet:
                   "qmann_hops_packed")
         return (u_out, tobj) if taps else u_out
 
+    def hops_shared_packed(self, key_planes, vals, n_slots, u0, taps=False):
+        """qmann_hops_shared_packed: Hamming V0 / V1 attention on ONE memory for every query.  key_planes int64
+        [H or 1][n_slots][Dp/64][num_bit], vals int8 [H or 1][n_slots][Dp] (1: tied hops, both strides 0); u0 [B][D] float.
+        taps: score_codes / scores / probs [H][B][n_slots], o / u [B][H][D]."""
+        B = u0.shape[0]
+        nb = key_planes.shape[-1]
+        assert vals.shape in ((self.H, n_slots, self.Dp), (1, n_slots, self.Dp))
+        assert key_planes.shape == (vals.shape[0], n_slots, self.Dp // 64, nb)
+        assert key_planes.is_contiguous() and vals.is_contiguous()
+        u_out = torch.empty_like(u0)
+        tp, tobj = None, None
+        if taps:
+            tobj = HopTaps(
+                torch.zeros((self.H, B, n_slots), dtype=torch.int32, device=self.dev),
+                torch.zeros((self.H, B, n_slots), dtype=torch.float32, device=self.dev),
+                torch.zeros((self.H, B, n_slots), dtype=torch.float32, device=self.dev),
+                torch.zeros((B, self.H, self.D), dtype=torch.float32, device=self.dev),
+                torch.zeros((B, self.H, self.D), dtype=torch.float32, device=self.dev))
+            tp = abi.Taps(tobj.score_codes.data_ptr(), tobj.scores.data_ptr(), tobj.probs.data_ptr(),
+                          tobj.o.data_ptr(), tobj.u.data_ptr())
+        per_hop = vals.shape[0] == self.H
+        key_stride = n_slots * (self.Dp // 64) * nb * 8 if per_hop else 0         # one plane for several hops: tied
+        val_stride = n_slots * self.Dp if per_hop else 0
+        abi.check(abi.lib.qmann_hops_shared_packed(C.byref(self.net), _ptr(key_planes), key_stride, _ptr(vals), val_stride,
+                                                   n_slots, _ptr(u0), _ptr(u_out), C.byref(tp) if tp else None, B, self._s()),
+                  "qmann_hops_shared_packed")
+        return (u_out, tobj) if taps else u_out
+
     def answer(self, u, answer=None, want_probs=False, serial=False):
         """serial=True: qmann_answer_f32_serial (the reference's order of additions, bit-equal logits); default: the library's
         choice (the fused bf16 form at the bAbI shapes, within 1e-5 on the probabilities)"""
@@ -437,6 +465,23 @@ class HostModel:
                                                            _ptr(question_words), question_words.shape[1], B, _ptr(answer),
                                                            _ptr(pred), _ptr(cost), _ptr(match), self._s()),
                   "qmann_model_forward_shared_words")
+        return pred, cost, match
+
+    def memorize_words(self, story_words):
+        """qmann_model_memorize_words: embed (and for V0 / V1 models pack) the knowledge base story_words [n_rows][W] once; the
+        model keeps it until the next memorize_words"""
+        abi.check(abi.lib.qmann_model_memorize_words(self.h, _ptr(story_words), story_words.shape[0], story_words.shape[1],
+                                                     self._s()), "qmann_model_memorize_words")
+
+    def memory_rows(self) -> int:
+        return int(abi.lib.qmann_model_memory_rows(self.h))
+
+    def ask_words(self, question_words, answer=None):
+        """qmann_model_ask_words: every question of question_words [B][Wq] attends to the memorised knowledge base"""
+        B = question_words.shape[0]
+        pred, cost, match = self._out(B, answer)
+        abi.check(abi.lib.qmann_model_ask_words(self.h, _ptr(question_words), question_words.shape[1], B, _ptr(answer),
+                                                _ptr(pred), _ptr(cost), _ptr(match), self._s()), "qmann_model_ask_words")
         return pred, cost, match
 
     def forward_bow(self, story, question, row_off, max_slots, answer=None):
