@@ -158,6 +158,29 @@ int qmann_hops_shared_i8(const qmann_net *net, const int8_t *keys, const int8_t 
                          uint32_t n_slots, const float *u0, float *u_out, const qmann_taps *taps,
                          uint32_t n_query, void *stream);
 
+/* qmann_hops_shared_i8 with the SLOTS cut into slices (csrc/batch_hops_shared_split.hip): for memories too long for LDS (up to
+ * 2^24 slots) and for batches of so few questions that one workgroup per tile of queries leaves most compute units idle.
+ * Arguments and taps as qmann_hops_shared_i8; QMANN_ATT_FIXED only, and every qmann_net field that call honours is honoured.
+ * Results equal those of qmann_hops_shared_i8 bit for bit wherever that call runs (scores are int8 codes and the softmax is
+ * computed from integer histogram counts, which add across workgroups in any order); beyond its cap they are those of
+ * qmann_hops_i8 on copies of the plane, had LDS no limit.
+ * Per hop two kernels on `stream` (scan: query tiles x slices; finish: one workgroup per query), behind one hipMemsetAsync of
+ * the histograms: 1 + 2 n_hop ordered nodes, no library scratch, no second stream, no allocation -- it can be captured in a graph.
+ * ws: the CALLER's workspace, 16-byte aligned, at least qmann_hops_shared_split_ws_bytes(net, n_slots, n_query) bytes (linear in
+ * n_query: score bytes [n_query][n_slots rounded up to 16], uint32 histograms [n_hop][n_query][256], float u [n_query][256]).
+ * Its contents need not survive between calls; two calls that may run at the same time need a workspace each.
+ * n_slices: slices wanted, 0 = the library's choice (qmann_hops_shared_split_slices).  A slice is a multiple of 16 rows except
+ * the last, so a wish larger than ceil(n_slots / 16) is clamped to that (and to what keeps tiles x slices below 2^31).
+ * The query tile is the library's choice; QMANN_SHARED_QT forces one.
+ * Nothing is launched and the code returned is: QMANN_EUNSUPPORTED for another attention mode or a dim_emb_pad outside
+ * {64, 128, 256}; QMANN_EINVAL for null pointers, a null or misaligned ws, ws_bytes below the helper's figure, n_slots = 0;
+ * QMANN_ERANGE for n_slots > 2^24, 2^24 queries or more, a word length above 8.  n_query = 0: QMANN_OK. */
+size_t qmann_hops_shared_split_ws_bytes(const qmann_net *net, uint32_t n_slots, uint32_t n_query);
+uint32_t qmann_hops_shared_split_slices(uint32_t n_slots, uint32_t dim_emb_pad, uint32_t n_query);
+int qmann_hops_shared_split_i8(const qmann_net *net, const int8_t *keys, const int8_t *vals, size_t hop_stride,
+                               uint32_t n_slots, const float *u0, float *u_out, const qmann_taps *taps, uint32_t n_query,
+                               uint32_t n_slices, void *ws, size_t ws_bytes, void *stream);
+
 /* Packed binary codes for the Hamming forms: sign-magnitude bytes [rows][Dp] -> bit planes
  * uint64 [rows][Dp/64][num_bit] (plane 0 = sign bits, plane i = magnitude bit 7-i; bit b of a word
  * is column 64.g + b).  num_bit in 1..8.  sm_codes 16-byte aligned, planes 8-byte aligned (QMANN_EINVAL otherwise). */

@@ -125,6 +125,18 @@ int qmann_model_ask_words(qmann_model *m, const uint16_t *question_words, uint32
                           const uint32_t *answer, uint32_t *pred, float *cost, uint32_t *match, void *stream);
 uint32_t qmann_model_memory_rows(const qmann_model *m);
 
+/* Opt-in: asks through qmann_hops_shared_split_i8 (qmann_batch.h).  Without this call every call above behaves as described.
+ * The model allocates `scratch_bytes` of workspace HERE (freed by qmann_model_destroy; never regrown inside an ask, so asks
+ * still allocate nothing and stay capturable).  From then on qmann_model_memorize_words accepts QMANN_ATT_FIXED memories beyond
+ * the LDS cap, up to 2^24 rows, and returns QMANN_ERANGE where ONE query's share of workspace
+ * (qmann_hops_shared_split_ws_bytes(net, n_rows, 1)) exceeds the budget; qmann_model_ask_words takes the split call where the
+ * memory does not fit LDS (and, once measured, for small batches), in chunks of floor(budget / share) questions one after the
+ * other on the caller's stream.  Results are those of the unsplit ask, bit for bit.
+ * scratch_bytes = 0 turns the mode off and frees the workspace; a memorised memory that can no longer be asked (too long for
+ * LDS, or its share above a new budget) is forgotten.  A model whose attention mode is not QMANN_ATT_FIXED: QMANN_EUNSUPPORTED.
+ * The call waits for `stream` before it frees an earlier workspace; asks running on OTHER streams are the caller's to order. */
+int qmann_model_enable_split_asks(qmann_model *m, size_t scratch_bytes, void *stream);
+
 /* Forward from the reference's float bag-of-words pools (dev_m_test / dev_q_test, MemN2N.c:2337-2349):
  *   story [rows_total][dim_input] float, question [n_query][dim_input] float. */
 int qmann_model_forward_bow(qmann_model *m, const float *story, uint32_t rows_total, const float *question,

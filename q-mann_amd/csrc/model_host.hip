@@ -98,6 +98,10 @@ struct qmann_model {
     uint64_t *mem_planes = nullptr;
     uint32_t mem_rows = 0;
     size_t mem_cap_rows = 0;
+    // qmann_model_enable_split_asks: the workspace of qmann_hops_shared_split_i8, allocated by that call and never inside an ask;
+    // split_bytes = 0: the mode is off
+    void *split_ws = nullptr;
+    size_t split_bytes = 0;
     bool answer_exact = false;   // rt.h::qm_model_answer_exact: the float answer layer keeps the serial order of additions
 };
 
@@ -119,6 +123,19 @@ bool regrow(T **p, size_t n)
         return false;
     }
     return true;
+}
+
+constexpr size_t kAskLdsLimit = 160 * 1024 - 1024;        // what the shared-plane hop calls allow one query (their QMANN_ERANGE)
+// Asks of at most this many questions take the split call although the memory fits LDS.  NOT MEASURED (tools/shared_split_ab.py,
+// DESIGN.md section 5 "Measured, shared plane, split"): 0 = only memories that do not fit LDS take it.
+constexpr uint32_t kSplitAskMaxQueries = 0;
+
+// does an ask of the memorised FIXED memory go through the split call?
+bool ask_splits(const qmann_model *m, uint32_t n_rows, uint32_t n_query)
+{
+    if (!m->split_bytes || m->net.attention_mode != QMANN_ATT_FIXED) return false;
+    if (qmann_hops_shared_split_ws_bytes(&m->net, n_rows, 1) > m->split_bytes) return false;
+    return qmann_hops_shared_lds_bytes(n_rows, 1) > kAskLdsLimit || n_query <= kSplitAskMaxQueries;
 }
 
 float *upload(const float *host, size_t n, hipStream_t st)
@@ -439,7 +456,7 @@ void qmann_model_destroy(qmann_model *m)
     DeviceScope on(m->device);
     auto drop = [](void *p) { if (p) QM_HIP(hipFree(p)); };
     drop(m->blob); drop(m->w_q);             // (w_a / w_c point into w_q's allocation)
-    drop(m->mem_keys); drop(m->mem_vals); drop(m->mem_planes);
+    drop(m->mem_keys); drop(m->mem_vals); drop(m->mem_planes); drop(m->split_ws);
     drop(m->keys); drop(m->vals); drop(m->planes); drop(m->u0); drop(m->u); drop(m->bow_words); drop(m->bow_irr);
     delete m;
 }
@@ -523,7 +540,8 @@ int qmann_model_memorize_words(qmann_model *m, const uint16_t *story_words, uint
     if (!story_words || n_rows == 0) return QMANN_EINVAL;
     // the memory's length against LDS now, so that an ask cannot fail late
     const size_t lds = packed ? qmann_hops_shared_packed_lds_bytes(&n, n_rows, 1) : qmann_hops_shared_lds_bytes(n_rows, 1);
-    if (lds > 160 * 1024 - 1024) return QMANN_ERANGE;
+    // (with split asks enabled a FIXED memory may be longer: then one query's share of the workspace must fit the budget)
+    if (lds > kAskLdsLimit && !(n_rows <= (1u << 24) && ask_splits(m, n_rows, 1))) return QMANN_ERANGE;
     DeviceScope on(m->device);
     m->mem_rows = 0;                                         // (a failure below leaves nothing memorised)
     const size_t n_plane = m->tied ? 1 : m->H;
@@ -564,7 +582,17 @@ int qmann_model_ask_words(qmann_model *m, const uint16_t *question_words, uint32
     if (packed_mode(m->net))
         rc = qmann_hops_shared_packed(&m->net, m->mem_planes, plane / m->Dp * (m->Dp / 64) * m->net.num_bit * 8, m->mem_vals, plane, S,
                                       m->u0, m->u, nullptr, n_query, stream);
-    else
+    else if (ask_splits(m, S, n_query)) {
+        // chunks of as many questions as the workspace holds, one after the other on the caller's stream
+        const size_t share = qmann_hops_shared_split_ws_bytes(&m->net, S, 1);
+        const size_t fit = m->split_bytes / share;
+        const uint32_t chunk = fit < n_query ? (uint32_t)fit : n_query;
+        for (uint32_t q0 = 0; q0 < n_query && !rc; q0 += chunk) {
+            const uint32_t nq = n_query - q0 < chunk ? n_query - q0 : chunk;
+            rc = qmann_hops_shared_split_i8(&m->net, m->mem_keys, m->mem_vals, plane, S, m->u0 + (size_t)q0 * m->D, m->u + (size_t)q0 * m->D,
+                                            nullptr, nq, 0, m->split_ws, m->split_bytes, stream);
+        }
+    } else
         rc = qmann_hops_shared_i8(&m->net, m->mem_keys, m->mem_vals, plane, S, m->u0, m->u, nullptr, n_query, stream);
     if (rc) return rc;
     rc = (m->answer_exact ? qmann_answer_f32_serial : qmann_answer_f32)(&m->net, m->w_ans, m->u, answer, pred, nullptr, cost, match, n_query, stream);
@@ -572,6 +600,34 @@ int qmann_model_ask_words(qmann_model *m, const uint16_t *question_words, uint32
 }
 
 uint32_t qmann_model_memory_rows(const qmann_model *m) { return m ? m->mem_rows : 0u; }
+
+int qmann_model_enable_split_asks(qmann_model *m, size_t scratch_bytes, void *stream)
+{
+    QmBatched qm_scope;
+    if (!m) return QMANN_EINVAL;
+    if (m->net.attention_mode != QMANN_ATT_FIXED) return QMANN_EUNSUPPORTED;
+    DeviceScope on(m->device);
+    if (m->split_ws) {
+        QM_HIP(hipStreamSynchronize((hipStream_t)stream));  // asks enqueued on it may still use the workspace that goes
+        QM_HIP(hipFree(m->split_ws));
+    }
+    m->split_ws = nullptr;
+    m->split_bytes = 0;
+    if (scratch_bytes) {
+        const hipError_t e = hipMalloc(&m->split_ws, scratch_bytes);
+        if (e != hipSuccess) {
+            fprintf(stderr, "[*E] HIP : qmann_model split workspace of %zu bytes : %s\n", scratch_bytes, hipGetErrorString(e));
+            (void)hipGetLastError();
+            m->split_ws = nullptr;
+        } else {
+            m->split_bytes = scratch_bytes;
+        }
+    }
+    // a memory only the split call can attend to, and no (or too small a) workspace for it: forgotten
+    if (m->mem_rows && qmann_hops_shared_lds_bytes(m->mem_rows, 1) > kAskLdsLimit && !ask_splits(m, m->mem_rows, 1)) m->mem_rows = 0;
+    if (scratch_bytes && !m->split_ws) return QMANN_EHIP;
+    return qm_scope.rc();
+}
 
 int qmann_model_forward_bow(qmann_model *m, const float *story, uint32_t rows_total, const float *question,
                             const uint32_t *row_off, uint32_t max_slots, uint32_t n_query, const uint32_t *answer,

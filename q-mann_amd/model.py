@@ -285,6 +285,33 @@ class QNet:
                   "qmann_hops_shared_i8")
         return (u_out, tobj) if taps else u_out
 
+    def hops_shared_split(self, keys, vals, n_slots, u0, n_slices=0, taps=False, u_out=None):
+        """qmann_hops_shared_split_i8: hops_shared with the slots cut into n_slices slices (0: the library's choice); the
+        workspace is allocated here, of the size the library's helper gives.  Arguments, results and taps as hops_shared."""
+        B = u0.shape[0]
+        assert keys.shape in ((self.H, n_slots, self.Dp), (1, n_slots, self.Dp)) and vals.shape == keys.shape
+        assert keys.is_contiguous() and vals.is_contiguous()
+        if u_out is None:
+            u_out = torch.empty_like(u0)
+        tp, tobj = None, None
+        if taps:
+            tobj = HopTaps(
+                torch.zeros((self.H, B, n_slots), dtype=torch.int32, device=self.dev),
+                torch.zeros((self.H, B, n_slots), dtype=torch.float32, device=self.dev),
+                torch.zeros((self.H, B, n_slots), dtype=torch.float32, device=self.dev),
+                torch.zeros((B, self.H, self.D), dtype=torch.float32, device=self.dev),
+                torch.zeros((B, self.H, self.D), dtype=torch.float32, device=self.dev))
+            tp = abi.Taps(tobj.score_codes.data_ptr(), tobj.scores.data_ptr(), tobj.probs.data_ptr(),
+                          tobj.o.data_ptr(), tobj.u.data_ptr())
+        nbytes = int(abi.lib.qmann_hops_shared_split_ws_bytes(C.byref(self.net), n_slots, B))
+        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=self.dev)       # (torch allocations are 16-byte aligned)
+        hop_stride = n_slots * self.Dp if keys.shape[0] == self.H else 0          # one plane for several hops: tied
+        abi.check(abi.lib.qmann_hops_shared_split_i8(C.byref(self.net), _ptr(keys), _ptr(vals), hop_stride, n_slots, _ptr(u0),
+                                                     _ptr(u_out), C.byref(tp) if tp else None, B, n_slices, _ptr(ws), nbytes,
+                                                     self._s()), "qmann_hops_shared_split_i8")
+        self._split_ws = ws                                                       # alive until the next call: the launch is asynchronous
+        return (u_out, tobj) if taps else u_out
+
     def pack_planes(self, sm_codes: torch.Tensor, num_bit: int) -> torch.Tensor:
         """sign-magnitude int8 [..., rows, Dp] -> packed bit planes int64 [..., rows, Dp/64, num_bit]."""
         assert sm_codes.dtype == torch.int8 and sm_codes.is_contiguous() and sm_codes.shape[-1] == self.Dp
@@ -472,6 +499,11 @@ class HostModel:
         model keeps it until the next memorize_words"""
         abi.check(abi.lib.qmann_model_memorize_words(self.h, _ptr(story_words), story_words.shape[0], story_words.shape[1],
                                                      self._s()), "qmann_model_memorize_words")
+
+    def enable_split_asks(self, nbytes: int):
+        """qmann_model_enable_split_asks: the model allocates nbytes of workspace and may then memorise memories beyond the LDS
+        cap and ask them through the slot-split hops; 0 turns the mode off"""
+        abi.check(abi.lib.qmann_model_enable_split_asks(self.h, int(nbytes), self._s()), "qmann_model_enable_split_asks")
 
     def memory_rows(self) -> int:
         return int(abi.lib.qmann_model_memory_rows(self.h))
