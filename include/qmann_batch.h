@@ -215,6 +215,33 @@ int qmann_hops_shared_packed(const qmann_net *net, const uint64_t *key_planes, s
                              const int8_t *vals, size_t val_hop_stride, uint32_t n_slots, const float *u0,
                              float *u_out, const qmann_taps *taps, uint32_t n_query, void *stream);
 
+/* qmann_hops_shared_packed with the SLOTS cut into slices (csrc/batch_hops_shared_split_ham.hip): for packed memories too long
+ * for LDS (up to 2^24 slots) and for batches of so few questions that one workgroup per tile of queries leaves most compute units
+ * idle.  Arguments, layouts and taps as qmann_hops_shared_packed; n_slices, ws and ws_bytes as qmann_hops_shared_split_i8.
+ * Results equal those of qmann_hops_shared_packed bit for bit wherever that call runs (V0: the softmax is computed from integer
+ * counts of the scores, which add across workgroups in any order; V1: the per-slot softmax runs in one workgroup per query on the
+ * same int16 scores, in the same order); beyond its cap they are those of qmann_hops_packed on copies, had LDS no limit.
+ * Per hop two kernels on `stream` (scan: query tiles x slices; finish: one workgroup per query), for V0 behind one
+ * hipMemsetAsync of the bins: at most 1 + 2 n_hop ordered nodes, no library scratch, no second stream, no allocation -- it can be
+ * captured in a graph.
+ * ws: the CALLER's workspace, 16-byte aligned, at least qmann_hops_shared_split_packed_ws_bytes(net, n_slots, n_query) bytes =
+ *   n_query . ( 2 . (n_slots rounded up to 16)                                   int16 scores
+ *             + (V0 only) 4 . n_hop . ((num_bit . dim_emb + 1) rounded up to 4)  uint32 bins
+ *             + 1024 )                                                           float u [256]
+ * Its contents need not survive between calls; two calls that may run at the same time need a workspace each.
+ * n_slices: slices wanted, 0 = the library's choice (qmann_hops_shared_split_packed_slices).  A slice is a multiple of 16 rows
+ * except the last, so a wish larger than ceil(n_slots / 16) is clamped to that (and to what keeps tiles x slices below 2^31).
+ * The query tile is the library's choice (the scan's LDS holds eight queries at any size); QMANN_SHARED_QT forces one.
+ * Nothing is launched and the code returned is: every refusal of qmann_hops_shared_packed except the QMANN_ERANGE of a memory too
+ * long for LDS; QMANN_EINVAL for a null or misaligned ws or a ws_bytes below the helper's figure; QMANN_ERANGE for n_slots > 2^24
+ * and for 2^24 queries or more.  n_query = 0: QMANN_OK.  The helpers answer 0 where a call would launch nothing. */
+size_t qmann_hops_shared_split_packed_ws_bytes(const qmann_net *net, uint32_t n_slots, uint32_t n_query);
+uint32_t qmann_hops_shared_split_packed_slices(const qmann_net *net, uint32_t n_slots, uint32_t n_query);
+int qmann_hops_shared_split_packed(const qmann_net *net, const uint64_t *key_planes, size_t key_hop_stride,
+                                   const int8_t *vals, size_t val_hop_stride, uint32_t n_slots, const float *u0,
+                                   float *u_out, const qmann_taps *taps, uint32_t n_query, uint32_t n_slices, void *ws,
+                                   size_t ws_bytes, void *stream);
+
 /* Answer layer for a batch: logits = W_ans . u (float, ds_ans is always float: MemN2N.c:902-906),
  * softmax over V, arg-max with ties to the highest index, and -- when `answer` is given -- the
  * test-phase bookkeeping of cross_entropy_run mode 3 (cost += -p[answer], match += pred==answer).

@@ -137,6 +137,14 @@ uint32_t qmann_model_memory_rows(const qmann_model *m);
  * The call waits for `stream` before it frees an earlier workspace; asks running on OTHER streams are the caller's to order. */
 int qmann_model_enable_split_asks(qmann_model *m, size_t scratch_bytes, void *stream);
 
+/* The same opt-in for QMANN_ATT_HAMMING_V0 / _V1 models (the ones qmann_model_memorize_words accepts): asks through
+ * qmann_hops_shared_split_packed.  The contract is that of qmann_model_enable_split_asks with that call's helper: memories beyond
+ * the LDS cap of qmann_hops_shared_packed, up to 2^24 rows, are embedded and packed; QMANN_ERANGE at memorize where ONE query's
+ * share (qmann_hops_shared_split_packed_ws_bytes(net, n_rows, 1)) exceeds the budget; asks of such a memory go in chunks of
+ * floor(budget / share) questions; a memory that fits LDS is asked as before, bit for bit.  scratch_bytes = 0 turns the mode off
+ * and forgets a memory that can no longer be asked.  Any other model: QMANN_EUNSUPPORTED. */
+int qmann_model_enable_split_asks_packed(qmann_model *m, size_t scratch_bytes, void *stream);
+
 /* Forward from the reference's float bag-of-words pools (dev_m_test / dev_q_test, MemN2N.c:2337-2349):
  *   story [rows_total][dim_input] float, question [n_query][dim_input] float. */
 int qmann_model_forward_bow(qmann_model *m, const float *story, uint32_t rows_total, const float *question,

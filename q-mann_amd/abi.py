@@ -162,6 +162,10 @@ _proto("qmann_hops_shared_split_i8", C.c_int, [C.POINTER(Net), _vp, _vp, C.c_siz
                                                C.POINTER(Taps), C.c_uint32, C.c_uint32, _vp, C.c_size_t, _vp])
 _proto("qmann_hops_shared_packed", C.c_int, [C.POINTER(Net), _vp, C.c_size_t, _vp, C.c_size_t, C.c_uint32, _vp, _vp,
                                              C.POINTER(Taps), C.c_uint32, _vp])
+_proto("qmann_hops_shared_split_packed_ws_bytes", C.c_size_t, [C.POINTER(Net), C.c_uint32, C.c_uint32])
+_proto("qmann_hops_shared_split_packed_slices", C.c_uint32, [C.POINTER(Net), C.c_uint32, C.c_uint32])
+_proto("qmann_hops_shared_split_packed", C.c_int, [C.POINTER(Net), _vp, C.c_size_t, _vp, C.c_size_t, C.c_uint32, _vp, _vp,
+                                                   C.POINTER(Taps), C.c_uint32, C.c_uint32, _vp, C.c_size_t, _vp])
 _proto("qmann_hops_shared_packed_lds_bytes", C.c_size_t, [C.POINTER(Net), C.c_uint32, C.c_uint32])
 _proto("qmann_hops_shared_packed_tile", C.c_uint32, [C.POINTER(Net), C.c_uint32, C.c_uint32])
 _proto("qmann_answer_f32", C.c_int, [C.POINTER(Net), _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, _vp])
@@ -207,6 +211,7 @@ _proto("qmann_model_ask_words", C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _vp,
 _proto("qmann_model_memory_rows", C.c_uint32, [_vp])
 _proto("qmann_model_forward_bow", C.c_int, [_vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, _vp])
 _proto("qmann_model_enable_split_asks", C.c_int, [_vp, C.c_size_t, _vp])
+_proto("qmann_model_enable_split_asks_packed", C.c_int, [_vp, C.c_size_t, _vp])
 _proto("qmann_model_last_u", _vp, [_vp])
 _proto("qmann_weights_save", C.c_int, [C.c_char_p, C.POINTER(Weights), C.POINTER(Fmt)])
 _proto("qmann_weights_load", C.c_int, [C.c_char_p, C.POINTER(Weights), C.c_int, C.POINTER(Fmt)])

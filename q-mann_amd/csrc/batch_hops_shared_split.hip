@@ -2,8 +2,8 @@
 // queries) with the SLOTS cut into slices, for the two cases a workgroup that walks the whole memory alone leaves open: a memory
 // whose score bytes do not fit LDS, and a batch of so few questions that most compute units would stand idle.
 //
-// Fixed-point attention (QMANN_ATT_FIXED) only.  The packed Hamming forms (batch_hops_shared_ham.hip), APPX and float attention
-// are follow-ups: their score tables and float sums are not covered by the argument below.
+// Fixed-point attention (QMANN_ATT_FIXED) only.  The packed Hamming forms have their own unit (batch_hops_shared_split_ham.hip:
+// qmann_hops_shared_split_packed); APPX and float attention are follow-ups: their float sums are not covered by the argument below.
 //
 // Why the cut is exact: a hop's scores are int8 codes, its softmax is computed from a 256-bin histogram of those codes
 // (hops_common.h::hist_softmax_survivors) and its read-out is an integer sum over the surviving rows.  Histogram counts are

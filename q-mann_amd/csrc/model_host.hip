@@ -98,8 +98,8 @@ struct qmann_model {
     uint64_t *mem_planes = nullptr;
     uint32_t mem_rows = 0;
     size_t mem_cap_rows = 0;
-    // qmann_model_enable_split_asks: the workspace of qmann_hops_shared_split_i8, allocated by that call and never inside an ask;
-    // split_bytes = 0: the mode is off
+    // qmann_model_enable_split_asks / _packed: the workspace of qmann_hops_shared_split_i8 / _split_packed (a model has one
+    // attention mode, hence one of the two), allocated by that call and never inside an ask; split_bytes = 0: the mode is off
     void *split_ws = nullptr;
     size_t split_bytes = 0;
     bool answer_exact = false;   // rt.h::qm_model_answer_exact: the float answer layer keeps the serial order of additions
@@ -129,13 +129,68 @@ constexpr size_t kAskLdsLimit = 160 * 1024 - 1024;        // what the shared-pla
 // Asks of at most this many questions take the split call although the memory fits LDS.  NOT MEASURED (tools/shared_split_ab.py,
 // DESIGN.md section 5 "Measured, shared plane, split"): 0 = only memories that do not fit LDS take it.
 constexpr uint32_t kSplitAskMaxQueries = 0;
+// The same for packed memories (qmann_hops_shared_split_packed).  Measured at 10 000 slots only (tools/shared_split_ham_ab.py,
+// DESIGN.md section 5 "Measured, shared plane, split, Hamming"): there the split call beats the unsplit one beyond the two spreads
+// at EVERY batch size for V1 (128 x 8 bits) and only from 1 024 questions up for V0 (256 x 1 bit), where it loses 8 to 17 % below
+// 64 -- so no threshold "small batches take the split call" holds for both, and shorter memories are NOT MEASURED.  It stays 0:
+// only memories that do not fit LDS take the split call.  (A rule by mode and length is the follow-up the table asks for.)
+constexpr uint32_t kSplitAskPackedMaxQueries = 0;
 
-// does an ask of the memorised FIXED memory go through the split call?
+// a Hamming model the packed shared-plane calls accept (what qmann_hops_shared_packed would refuse, said ahead of a launch)
+bool packed_model_ok(const qmann_model *m)
+{
+    const qmann_net &n = m->net;
+    if (!packed_mode(n)) return false;
+    const uint32_t nb = n.num_bit;
+    if ((nb != 1 && nb != 2 && nb != 4 && nb != 8) || (m->Dp / 64) * nb * 8 < 16) return false;
+    for (uint32_t h = 0; h < m->H; h++)
+        if (n.att[h].iwl + n.att[h].frac != 7 || n.att[h].iwl < 1) return false;
+    return true;
+}
+
+// one query's LDS in the unsplit shared-plane call of the model's mode, and its share of a split call's workspace
+size_t ask_lds_bytes(const qmann_model *m, uint32_t n_rows)
+{
+    return packed_mode(m->net) ? qmann_hops_shared_packed_lds_bytes(&m->net, n_rows, 1) : qmann_hops_shared_lds_bytes(n_rows, 1);
+}
+size_t ask_split_share(const qmann_model *m, uint32_t n_rows)
+{
+    return packed_mode(m->net) ? qmann_hops_shared_split_packed_ws_bytes(&m->net, n_rows, 1) : qmann_hops_shared_split_ws_bytes(&m->net, n_rows, 1);
+}
+
+// does an ask of the memorised memory go through the split call of the model's mode?  (split_bytes is non-zero only on a model
+// whose mode has one: the two enable calls see to that)
 bool ask_splits(const qmann_model *m, uint32_t n_rows, uint32_t n_query)
 {
-    if (!m->split_bytes || m->net.attention_mode != QMANN_ATT_FIXED) return false;
-    if (qmann_hops_shared_split_ws_bytes(&m->net, n_rows, 1) > m->split_bytes) return false;
-    return qmann_hops_shared_lds_bytes(n_rows, 1) > kAskLdsLimit || n_query <= kSplitAskMaxQueries;
+    if (!m->split_bytes) return false;
+    const size_t share = ask_split_share(m, n_rows);
+    if (!share || share > m->split_bytes) return false;
+    return ask_lds_bytes(m, n_rows) > kAskLdsLimit || n_query <= (packed_mode(m->net) ? kSplitAskPackedMaxQueries : kSplitAskMaxQueries);
+}
+
+// the body of the two enable calls: the workspace replaced by one of scratch_bytes (0: none), a memory that can no longer be
+// asked forgotten
+int set_split_workspace(qmann_model *m, size_t scratch_bytes, void *stream)
+{
+    if (m->split_ws) {
+        QM_HIP(hipStreamSynchronize((hipStream_t)stream));  // asks enqueued on it may still use the workspace that goes
+        QM_HIP(hipFree(m->split_ws));
+    }
+    m->split_ws = nullptr;
+    m->split_bytes = 0;
+    if (scratch_bytes) {
+        const hipError_t e = hipMalloc(&m->split_ws, scratch_bytes);
+        if (e != hipSuccess) {
+            fprintf(stderr, "[*E] HIP : qmann_model split workspace of %zu bytes : %s\n", scratch_bytes, hipGetErrorString(e));
+            (void)hipGetLastError();
+            m->split_ws = nullptr;
+        } else {
+            m->split_bytes = scratch_bytes;
+        }
+    }
+    // a memory only the split call can attend to, and no (or too small a) workspace for it: forgotten
+    if (m->mem_rows && ask_lds_bytes(m, m->mem_rows) > kAskLdsLimit && !ask_splits(m, m->mem_rows, 1)) m->mem_rows = 0;
+    return (scratch_bytes && !m->split_ws) ? QMANN_EHIP : QMANN_OK;
 }
 
 float *upload(const float *host, size_t n, hipStream_t st)
@@ -531,16 +586,11 @@ int qmann_model_memorize_words(qmann_model *m, const uint16_t *story_words, uint
     const qmann_net &n = m->net;
     const bool packed = packed_mode(n);
     if (!packed && n.attention_mode != QMANN_ATT_FIXED) return QMANN_EUNSUPPORTED;      // (what the shared-plane hop calls cover)
-    if (packed) {                                            // what qmann_hops_shared_packed would refuse, said here
-        const uint32_t nb = n.num_bit;
-        if ((nb != 1 && nb != 2 && nb != 4 && nb != 8) || (m->Dp / 64) * nb * 8 < 16) return QMANN_EUNSUPPORTED;
-        for (uint32_t h = 0; h < m->H; h++)
-            if (n.att[h].iwl + n.att[h].frac != 7 || n.att[h].iwl < 1) return QMANN_EUNSUPPORTED;
-    }
+    if (packed && !packed_model_ok(m)) return QMANN_EUNSUPPORTED;       // what qmann_hops_shared_packed would refuse, said here
     if (!story_words || n_rows == 0) return QMANN_EINVAL;
     // the memory's length against LDS now, so that an ask cannot fail late
-    const size_t lds = packed ? qmann_hops_shared_packed_lds_bytes(&n, n_rows, 1) : qmann_hops_shared_lds_bytes(n_rows, 1);
-    // (with split asks enabled a FIXED memory may be longer: then one query's share of the workspace must fit the budget)
+    const size_t lds = ask_lds_bytes(m, n_rows);
+    // (with split asks enabled a memory may be longer: then one query's share of the workspace must fit the budget)
     if (lds > kAskLdsLimit && !(n_rows <= (1u << 24) && ask_splits(m, n_rows, 1))) return QMANN_ERANGE;
     DeviceScope on(m->device);
     m->mem_rows = 0;                                         // (a failure below leaves nothing memorised)
@@ -579,20 +629,24 @@ int qmann_model_ask_words(qmann_model *m, const uint16_t *question_words, uint32
     const size_t plane = m->tied ? 0 : (size_t)S * m->Dp;
     rc = qmann_embed_query_idx(&m->net, question_words, max_q_words, m->t_q, m->u0, n_query, stream);
     if (rc) return rc;
-    if (packed_mode(m->net))
-        rc = qmann_hops_shared_packed(&m->net, m->mem_planes, plane / m->Dp * (m->Dp / 64) * m->net.num_bit * 8, m->mem_vals, plane, S,
-                                      m->u0, m->u, nullptr, n_query, stream);
-    else if (ask_splits(m, S, n_query)) {
+    const bool packed = packed_mode(m->net);
+    const size_t key_plane = plane / m->Dp * (m->Dp / 64) * m->net.num_bit * 8;     // (packed: bytes of one hop's key planes)
+    if (ask_splits(m, S, n_query)) {
         // chunks of as many questions as the workspace holds, one after the other on the caller's stream
-        const size_t share = qmann_hops_shared_split_ws_bytes(&m->net, S, 1);
-        const size_t fit = m->split_bytes / share;
+        const size_t fit = m->split_bytes / ask_split_share(m, S);
         const uint32_t chunk = fit < n_query ? (uint32_t)fit : n_query;
         for (uint32_t q0 = 0; q0 < n_query && !rc; q0 += chunk) {
             const uint32_t nq = n_query - q0 < chunk ? n_query - q0 : chunk;
-            rc = qmann_hops_shared_split_i8(&m->net, m->mem_keys, m->mem_vals, plane, S, m->u0 + (size_t)q0 * m->D, m->u + (size_t)q0 * m->D,
-                                            nullptr, nq, 0, m->split_ws, m->split_bytes, stream);
+            const float *u0 = m->u0 + (size_t)q0 * m->D;
+            float *u = m->u + (size_t)q0 * m->D;
+            rc = packed ? qmann_hops_shared_split_packed(&m->net, m->mem_planes, key_plane, m->mem_vals, plane, S, u0, u, nullptr, nq, 0,
+                                                         m->split_ws, m->split_bytes, stream)
+                        : qmann_hops_shared_split_i8(&m->net, m->mem_keys, m->mem_vals, plane, S, u0, u, nullptr, nq, 0, m->split_ws,
+                                                     m->split_bytes, stream);
         }
-    } else
+    } else if (packed)
+        rc = qmann_hops_shared_packed(&m->net, m->mem_planes, key_plane, m->mem_vals, plane, S, m->u0, m->u, nullptr, n_query, stream);
+    else
         rc = qmann_hops_shared_i8(&m->net, m->mem_keys, m->mem_vals, plane, S, m->u0, m->u, nullptr, n_query, stream);
     if (rc) return rc;
     rc = (m->answer_exact ? qmann_answer_f32_serial : qmann_answer_f32)(&m->net, m->w_ans, m->u, answer, pred, nullptr, cost, match, n_query, stream);
@@ -607,26 +661,18 @@ int qmann_model_enable_split_asks(qmann_model *m, size_t scratch_bytes, void *st
     if (!m) return QMANN_EINVAL;
     if (m->net.attention_mode != QMANN_ATT_FIXED) return QMANN_EUNSUPPORTED;
     DeviceScope on(m->device);
-    if (m->split_ws) {
-        QM_HIP(hipStreamSynchronize((hipStream_t)stream));  // asks enqueued on it may still use the workspace that goes
-        QM_HIP(hipFree(m->split_ws));
-    }
-    m->split_ws = nullptr;
-    m->split_bytes = 0;
-    if (scratch_bytes) {
-        const hipError_t e = hipMalloc(&m->split_ws, scratch_bytes);
-        if (e != hipSuccess) {
-            fprintf(stderr, "[*E] HIP : qmann_model split workspace of %zu bytes : %s\n", scratch_bytes, hipGetErrorString(e));
-            (void)hipGetLastError();
-            m->split_ws = nullptr;
-        } else {
-            m->split_bytes = scratch_bytes;
-        }
-    }
-    // a memory only the split call can attend to, and no (or too small a) workspace for it: forgotten
-    if (m->mem_rows && qmann_hops_shared_lds_bytes(m->mem_rows, 1) > kAskLdsLimit && !ask_splits(m, m->mem_rows, 1)) m->mem_rows = 0;
-    if (scratch_bytes && !m->split_ws) return QMANN_EHIP;
-    return qm_scope.rc();
+    const int rc = set_split_workspace(m, scratch_bytes, stream);
+    return rc ? rc : qm_scope.rc();
+}
+
+int qmann_model_enable_split_asks_packed(qmann_model *m, size_t scratch_bytes, void *stream)
+{
+    QmBatched qm_scope;
+    if (!m) return QMANN_EINVAL;
+    if (!packed_model_ok(m)) return QMANN_EUNSUPPORTED;
+    DeviceScope on(m->device);
+    const int rc = set_split_workspace(m, scratch_bytes, stream);
+    return rc ? rc : qm_scope.rc();
 }
 
 int qmann_model_forward_bow(qmann_model *m, const float *story, uint32_t rows_total, const float *question,

@@ -371,6 +371,39 @@ class QNet:
                   "qmann_hops_shared_packed")
         return (u_out, tobj) if taps else u_out
 
+    def hops_shared_split_packed(self, key_planes, vals, n_slots, u0, n_slices=0, taps=False, u_out=None, ws=None):
+        """qmann_hops_shared_split_packed: hops_shared_packed with the slots cut into n_slices slices (0: the library's choice).
+        ws: a uint8 workspace of the caller's (16-byte aligned, at least the helper's size); None: allocated here, of the size
+        the library's helper gives.  Arguments, results and taps as hops_shared_packed."""
+        B = u0.shape[0]
+        nb = key_planes.shape[-1]
+        assert vals.shape in ((self.H, n_slots, self.Dp), (1, n_slots, self.Dp))
+        assert key_planes.shape == (vals.shape[0], n_slots, self.Dp // 64, nb)
+        assert key_planes.is_contiguous() and vals.is_contiguous()
+        if u_out is None:
+            u_out = torch.empty_like(u0)
+        tp, tobj = None, None
+        if taps:
+            tobj = HopTaps(
+                torch.zeros((self.H, B, n_slots), dtype=torch.int32, device=self.dev),
+                torch.zeros((self.H, B, n_slots), dtype=torch.float32, device=self.dev),
+                torch.zeros((self.H, B, n_slots), dtype=torch.float32, device=self.dev),
+                torch.zeros((B, self.H, self.D), dtype=torch.float32, device=self.dev),
+                torch.zeros((B, self.H, self.D), dtype=torch.float32, device=self.dev))
+            tp = abi.Taps(tobj.score_codes.data_ptr(), tobj.scores.data_ptr(), tobj.probs.data_ptr(),
+                          tobj.o.data_ptr(), tobj.u.data_ptr())
+        nbytes = int(abi.lib.qmann_hops_shared_split_packed_ws_bytes(C.byref(self.net), n_slots, B))
+        if ws is None:
+            ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=self.dev)   # (torch allocations are 16-byte aligned)
+        per_hop = vals.shape[0] == self.H
+        key_stride = n_slots * (self.Dp // 64) * nb * 8 if per_hop else 0         # one plane for several hops: tied
+        val_stride = n_slots * self.Dp if per_hop else 0
+        abi.check(abi.lib.qmann_hops_shared_split_packed(C.byref(self.net), _ptr(key_planes), key_stride, _ptr(vals), val_stride,
+                                                         n_slots, _ptr(u0), _ptr(u_out), C.byref(tp) if tp else None, B, n_slices,
+                                                         _ptr(ws), nbytes, self._s()), "qmann_hops_shared_split_packed")
+        self._split_ws = ws                                                       # alive until the next call: the launch is asynchronous
+        return (u_out, tobj) if taps else u_out
+
     def answer(self, u, answer=None, want_probs=False, serial=False):
         """serial=True: qmann_answer_f32_serial (the reference's order of additions, bit-equal logits); default: the library's
         choice (the fused bf16 form at the bAbI shapes, within 1e-5 on the probabilities)"""
@@ -504,6 +537,12 @@ class HostModel:
         """qmann_model_enable_split_asks: the model allocates nbytes of workspace and may then memorise memories beyond the LDS
         cap and ask them through the slot-split hops; 0 turns the mode off"""
         abi.check(abi.lib.qmann_model_enable_split_asks(self.h, int(nbytes), self._s()), "qmann_model_enable_split_asks")
+
+    def enable_split_asks_packed(self, nbytes: int):
+        """qmann_model_enable_split_asks_packed: enable_split_asks for Hamming V0 / V1 models (asks of memories beyond the LDS cap
+        go through the slot-split hops on packed codes); 0 turns the mode off"""
+        abi.check(abi.lib.qmann_model_enable_split_asks_packed(self.h, int(nbytes), self._s()),
+                  "qmann_model_enable_split_asks_packed")
 
     def memory_rows(self) -> int:
         return int(abi.lib.qmann_model_memory_rows(self.h))
