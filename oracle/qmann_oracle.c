@@ -64,6 +64,26 @@ float qo_quant(float x, unsigned iwl, unsigned frac)
     return qo_fixed2float(qo_float2fixed(x, iwl, frac), frac);
 }
 
+/* CUDA_FLOAT_QUANT of a DOUBLE expression.  The macro computes in the type of its argument, and the sigmoid kernels
+ * hand it one that is a double (lib/layer_cuda.cu:1682, :1711): the limits stay floats, the product with 2^frac and
+ * the truncation are done in double.  Rounding the expression to float first would turn sigmoid(x) = 1 - 1e-8 into 1. */
+static float quant_d(double x, unsigned iwl, unsigned frac)
+{
+    if (iwl + frac == 0) return (x >= 0.0) ? 1.0f : -1.0f;
+    const int32_t M = (int32_t)((1u << (iwl + frac)) - 1u);
+    const float scale = (float)(1 << frac);
+    const float maxf = (float)M / scale;
+    int32_t t;
+    if (x > maxf) t = M;
+    else if (x < -1 * maxf) t = -M;
+    else {
+        const double p = x * (1 << frac);
+        t = p >= 2147483648.0 ? INT32_MAX : p <= -2147483648.0 ? INT32_MIN : (int32_t)p;
+    }
+    if (t == INT32_MIN) return 0.0f;                /* the "minus zero" word */
+    return (float)t / scale;
+}
+
 /* lib/layer_cuda.h:258 (CUDA_FIXED_MUL): result in a's format */
 float qo_fixed_mul(float a, float b, unsigned iwl_a, unsigned frac_a,
                    unsigned iwl_b, unsigned frac_b)
@@ -145,7 +165,11 @@ void qo_activation_fwd(const float *in, float *out, unsigned dim, const char *ac
 {
     for (unsigned i = 0; i < dim; i++) {
         float v;
-        if (!strcmp(act, "SIGMOID")) v = (float)(1.0 / (1.0 + expf(-in[i])));
+        if (!strcmp(act, "SIGMOID")) {
+            const double sg = 1.0 / (1.0 + expf(-in[i]));          /* :1682: the double goes into the quantiser */
+            out[i] = f_fixed ? quant_d(sg, iwl, frac) : (float)sg;
+            continue;
+        }
         else if (!strcmp(act, "RELU")) v = (in[i] > 0.0f) ? in[i] : 0.0f;
         else v = in[i];
         out[i] = f_fixed ? qo_quant(v, iwl, frac) : v;
@@ -530,7 +554,7 @@ void qo_dense_bwd(const float *w, float *w_del, const float *in, const float *ou
     if (act && !strcmp(act, "SIGMOID"))
         for (unsigned i = 0; i < dim_out; i++) {
             double g = grad_in[i] * out[i] * (1.0 - out[i]);
-            grad_in[i] = f_fixed ? qo_quant((float)g, iwl_w, frac_w) : (float)g;
+            grad_in[i] = f_fixed ? quant_d(g, iwl_w, frac_w) : (float)g;             /* :1711: quantised as a double */
         }
     else if (act && !strcmp(act, "RELU"))
         for (unsigned i = 0; i < dim_out; i++) {

@@ -117,6 +117,16 @@ _proto("cuda_dense_mat_bwd", None, [_vp] * 8 + [_u, _u, _u, _b, _u, _u, _u, _b])
 _proto("cuda_dense_mat_w_up", None, [_vp] * 8 + [_u, _u, _u, C.POINTER(_f), C.POINTER(_f), C.POINTER(_f), _b, _u, _u, _u, _b])
 _proto("cuda_dup_grad_bwd", None, [_vp] * 4 + [_u, _b, _u, _u, _u])
 _proto("cuda_activation_bwd", None, [_vp, _vp, _vp, C.c_char_p, _u, _b, _u, _u, _u])
+_proto("cuda_activation_init", None, [_vp, _vp, _u])
+_proto("cuda_scale_init", None, [_vp, _vp, _vp, _vp, C.POINTER(_f), _u])
+_proto("cuda_scale_bwd", None, [_vp] * 5 + [_u, _b, _u, _u, _u, _b])
+_proto("cuda_scale_w_up", None, [_vp, _vp, _u, _u, C.POINTER(_f), C.POINTER(_f), _b, _u, _u, _u, _b])
+_proto("cuda_mult_e_vec_init", None, [_vp] * 3 + [_u])
+_proto("cuda_mult_e_vec_fwd", None, [_vp] * 6 + [_u])
+_proto("cuda_mult_e_vec_bwd", None, [_vp] * 8 + [_u])
+_proto("cuda_mult_e_mat_init", None, [_vp] * 3 + [_u, _u])
+_proto("cuda_mult_e_mat_fwd", None, [_vp] * 6 + [_u, _u])
+_proto("cuda_mult_e_mat_bwd", None, [_vp] * 8 + [_u, _u])
 _proto("qmann_abi_set_softmax_base", None, [C.c_int])
 _proto("qmann_abi_symbol_count", _u, [])
 

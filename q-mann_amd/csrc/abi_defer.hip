@@ -195,6 +195,10 @@ size_t match_query(const std::vector<Op> &ops, size_t i, Sig &s, Query &qr)
         o = at(j);
         if (o && o->kind == kAct) {
             if (o->act != 2 || o->in != SV || o->r != s.D) return 0;
+            // the batched hop takes RELU(sv) as it is, on the grid of f_act[h]: a fixed-point RELU verb agrees with that only
+            // if its own format keeps every value of that grid (no fewer integer or fraction bits, no binarisation); a float
+            // one always does
+            if (o->fixed && (o->fa.iwl + o->fa.frac == 0 || o->fa.iwl < s.f_act[h].iwl || o->fa.frac < s.f_act[h].frac)) return 0;
             if (h == 0) s.has_relu = 1; else if (!s.has_relu) return 0;
             u_att = o->out;
             mix(o->out); j++;

@@ -254,8 +254,12 @@ __global__ void k_activation(const float *in, float *out, unsigned n, int act, b
     const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     float v = in[i];
-    if (act == kActSigmoid) v = (float)(1.0 / (1.0 + (double)expf(-v)));
-    else if (act == kActRelu) v = v > 0.0f ? v : 0.0f;
+    if (act == kActSigmoid) {
+        const double sg = 1.0 / (1.0 + (double)expf(-v));           // the reference quantises this double, not its float rounding
+        out[i] = fixed ? qm_quant_f64(sg, f.iwl, f.frac) : (float)sg;
+        return;
+    }
+    if (act == kActRelu) v = v > 0.0f ? v : 0.0f;
     out[i] = fixed ? qm_quant(v, f.iwl, f.frac) : v;
 }
 

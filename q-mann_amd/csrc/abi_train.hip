@@ -112,7 +112,7 @@ k_row_l2_accum(const float *__restrict__ in, float *out, unsigned cols)
     atomicAdd(out, sqrtf(sum));
 }
 
-// reference _cuda_mat_w_up (:1783-1830), then the accumulated gradient is cleared
+// reference _cuda_mat_w_up (:1783-1830), then the accumulated gradient is cleared (:3360, :3643)
 __global__ void k_mat_w_up(float *__restrict__ w_del, float *__restrict__ w, unsigned n, unsigned batch, float lr,
                            float lambda, float max_norm, const float *norm, bool fixed, QFmt f)
 {
@@ -146,8 +146,12 @@ __global__ void k_act_bwd(const float *out, const float *gin, float *gout, unsig
     const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     float g;
-    if (act == kActSigmoid) g = (float)((double)(gin[i] * out[i]) * (1.0 - (double)out[i]));
-    else if (act == kActRelu) g = out[i] > 0.0f ? gin[i] : 0.0f;
+    if (act == kActSigmoid) {
+        const double gd = (double)(gin[i] * out[i]) * (1.0 - (double)out[i]);      // quantised as a double (:1711)
+        gout[i] = fixed ? qm_quant_f64(gd, f.iwl, f.frac) : (float)gd;
+        return;
+    }
+    if (act == kActRelu) g = out[i] > 0.0f ? gin[i] : 0.0f;
     else g = gin[i];
     gout[i] = fixed ? qm_quant(g, f.iwl, f.frac) : g;
 }
@@ -251,6 +255,7 @@ __global__ void k_scale_bwd(const float *gin, const float *in, const float *w, f
     if (i < n) gout[i] = gin[i] * (*w);
 }
 
+// reference _cuda_w_up (:1834-1849); cuda_scale_w_up then clears the gradient itself (:4902)
 __global__ void k_scalar_w_up(float *w, float *w_del, unsigned batch, float lr, float lambda)
 {
     *w += lr / batch * (*w_del) + lr * lambda * (*w);

@@ -78,6 +78,25 @@ QM_HD float qm_quant(float x, uint32_t iwl, uint32_t frac)
     return qm_decode(k, frac);
 }
 
+// FLOAT_QUANT of a DOUBLE expression.  The reference's macro computes in the type of its argument, and its sigmoid kernels
+// hand it a double (lib/layer_cuda.cu:1682, :1711): the limits stay floats, the product with 2^frac and the truncation are done
+// in double.  Rounding the expression to float first would turn sigmoid(x) = 1 - 1e-8 into 1 and quantise that.
+QM_HD float qm_quant_f64(double x, uint32_t iwl, uint32_t frac)
+{
+    if (iwl + frac == 0) return (x >= 0.0) ? 1.0f : -1.0f;
+    const int32_t M = (int32_t)((1u << (iwl + frac)) - 1u);
+    const float maxf = qm_scale_down((float)M, frac);
+    int32_t k;
+    if (x > (double)maxf) k = M;
+    else if (x < -(double)maxf) k = -M;
+    else {
+        const double p = x * (double)(1u << frac);
+        k = p >= 2147483648.0 ? 2147483647 : p <= -2147483648.0 ? (int32_t)0x80000000 : (int32_t)p;
+    }
+    if (k == (int32_t)0x80000000) return 0.0f;
+    return qm_decode(k, frac);
+}
+
 // FIXED_MUL: Qa(Qa(a) * Qb(b))
 QM_HD float qm_fixed_mul(float a, float b, QFmt fa, QFmt fb)
 {
