@@ -264,6 +264,22 @@ int qmann_answer_f32_serial(const qmann_net *net, const float *w_ans, const floa
                             uint32_t *pred, float *probs, float *cost, uint32_t *match, uint32_t n_query,
                             void *stream);
 
+/* Ranked answers: per query the k most probable answers and their probabilities, without a [n_query][V] array anywhere.
+ *   top_idx [n_query][k] uint32, top_p [n_query][k] float; 1 <= k <= QMANN_MAX_TOPK, k <= dim_input.
+ * In terms of what qmann_answer_f32_serial writes for the same net, w_ans and u: top_p[q][j] is bit-equal to its
+ * probs[q][top_idx[q][j]], and row q lists the k entries of probs[q][:] that come first in the order "larger probability first,
+ * equal probabilities: higher index first" -- the tie rule of pred (lib/layer_cuda.cu:1918-1939), so top_idx[q][0] is the serial
+ * call's pred[q] always, also among probabilities that underflowed to 0.  Every softmax base.  The kernels are the serial-order
+ * ones of the shape with k rounds of their arg-max reduction behind the quotients (csrc/batch_answer.hip); the fused bf16 form
+ * has no ranked build, and there is none for qmann_answer_i8's int8 matrices: a host of those ranks dequantised weights here.
+ * One ordered step on `stream`, no allocation, no library scratch, no second stream: it can be captured in a graph.
+ * Nothing is launched and the code returned is: QMANN_EINVAL for null pointers, k = 0, k > QMANN_MAX_TOPK, k > dim_input,
+ * dim_emb = 0, dim_input = 0; QMANN_ERANGE where qmann_answer_f32_serial answers it (a query's LDS beyond 128 KiB, 2^24 queries
+ * or more); QMANN_OK for n_query = 0. */
+#define QMANN_MAX_TOPK 16
+int qmann_answer_topk_f32(const qmann_net *net, const float *w_ans, const float *u, uint32_t k,
+                          uint32_t *top_idx, float *top_p, uint32_t n_query, void *stream);
+
 /* The same answer layer when the answer matrix is on an int8 grid: w_ans_i8 [V][Dp] two's-complement
  * codes of Q(w_fmt); the projection runs on the int8 matrix cores (v_mfma_i32_16x16x64_i8).
  *   probs == NULL: one pass -- projection, running-maximum softmax statistics and arg-max in the accumulator registers, W

@@ -154,6 +154,19 @@ int qmann_model_forward_bow(qmann_model *m, const float *story, uint32_t rows_to
 /* device pointer to the last batch's final hop state u [n_query][D] (valid until the next call) */
 const float *qmann_model_last_u(const qmann_model *m);
 
+/* Ranked answers of the model's most recent batch: qmann_answer_topk_f32 (qmann_batch.h) on qmann_model_last_u with the model's
+ * own answer matrix -- top_idx / top_p [n_query][k] of the n_query that the last qmann_model_forward_words / _forward_shared_words
+ * / _ask_words / _forward_bow enqueued an answer layer for (a call of those that fails leaves no batch to rank).  One call for
+ * all four forwards.  The ranking is that of the SERIAL-ORDER layer: its first entry equals the forward's own pred wherever the
+ * two best probabilities differ by more than 1e-6 (the forward may have taken the fused bf16 form), and always under
+ * QMANN_ANSWER_EXACT.  Ordering is as for qmann_model_last_u: `stream` is the forward's stream, or the caller orders this call
+ * behind the forward; the next forward overwrites what it reads.  It allocates nothing.
+ * QMANN_EINVAL before any batch has run, and for what qmann_answer_topk_f32 refuses (k = 0, k > QMANN_MAX_TOPK, k > dim_input,
+ * null outputs). */
+int qmann_model_last_topk(qmann_model *m, uint32_t k, uint32_t *top_idx, float *top_p, void *stream);
+/* rows qmann_model_last_topk will write (the n_query of that last batch); 0 = no batch to rank */
+uint32_t qmann_model_last_n_query(const qmann_model *m);
+
 #ifdef __cplusplus
 }
 #endif

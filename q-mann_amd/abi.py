@@ -180,6 +180,7 @@ _proto("qmann_hops_shared_packed_lds_bytes", C.c_size_t, [C.POINTER(Net), C.c_ui
 _proto("qmann_hops_shared_packed_tile", C.c_uint32, [C.POINTER(Net), C.c_uint32, C.c_uint32])
 _proto("qmann_answer_f32", C.c_int, [C.POINTER(Net), _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, _vp])
 _proto("qmann_answer_f32_serial", C.c_int, [C.POINTER(Net), _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, _vp])
+_proto("qmann_answer_topk_f32", C.c_int, [C.POINTER(Net), _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp])
 _proto("qmann_answer_i8", C.c_int, [C.POINTER(Net), _vp, Fmt, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, _vp])
 _proto("qmann_embed_story", C.c_int, [C.POINTER(Net), _vp, C.c_uint32, C.POINTER(_vp), C.POINTER(_vp), _vp, _vp,
                                       C.c_size_t, _vp])
@@ -223,6 +224,8 @@ _proto("qmann_model_forward_bow", C.c_int, [_vp, _vp, C.c_uint32, _vp, _vp, C.c_
 _proto("qmann_model_enable_split_asks", C.c_int, [_vp, C.c_size_t, _vp])
 _proto("qmann_model_enable_split_asks_packed", C.c_int, [_vp, C.c_size_t, _vp])
 _proto("qmann_model_last_u", _vp, [_vp])
+_proto("qmann_model_last_topk", C.c_int, [_vp, C.c_uint32, _vp, _vp, _vp])
+_proto("qmann_model_last_n_query", C.c_uint32, [_vp])
 _proto("qmann_weights_save", C.c_int, [C.c_char_p, C.POINTER(Weights), C.POINTER(Fmt)])
 _proto("qmann_weights_load", C.c_int, [C.c_char_p, C.POINTER(Weights), C.c_int, C.POINTER(Fmt)])
 

@@ -14,11 +14,19 @@ namespace {
 // ---------------------------------------------------------------------------
 // PRECOMPUTED: logits come from a buffer (written by the MFMA projection below) instead of being
 // computed here.
-template <bool PRECOMPUTED>
+// TOPK (qmann_answer_topk_f32): instead of pred[q], the k best (probability, index) pairs of the query in the arg-max's own
+// order -- larger probability first, equal probabilities: higher index first -- go to tk.idx / tk.p [n_query][k].  The
+// probabilities are the ones the statements below leave in LDS, so they are the serial layer's bit for bit; k rounds of the
+// arg-max reduction, a taken entry marked by a negative value (probabilities are >= 0).  k <= V: every round finds an untaken one.
+// The ranked builds are instantiations of their own: the others take an EMPTY last argument and keep their device code.
+template <bool TOPK> struct AnsTopK {};
+template <> struct AnsTopK<true> { uint32_t *idx; float *p; uint32_t k; };
+
+template <bool PRECOMPUTED, bool TOPK = false>
 __global__ void __launch_bounds__(kBlock)
 k_answer(const float *__restrict__ w_ans, const float *__restrict__ u, const uint32_t *__restrict__ answer,
          uint32_t *__restrict__ pred, float *__restrict__ probs, float *cost, uint32_t *match, uint32_t D,
-         uint32_t V, uint32_t softmax_base, uint32_t n_query)
+         uint32_t V, uint32_t softmax_base, uint32_t n_query, const AnsTopK<TOPK> tk)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float *us = (float *)smem;            // [D]
@@ -80,7 +88,7 @@ k_answer(const float *__restrict__ w_ans, const float *__restrict__ u, const uin
         const float p = (softmax_base == QMANN_SOFTMAX_EXP) ? (float)((double)lg[v] / total)
                                                             : lg[v] / (float)total;
         lg[v] = p;
-        if (probs) probs[(size_t)q * V + v] = p;
+        if (!TOPK && probs) probs[(size_t)q * V + v] = p;
         if (!(bv > p)) { bv = p; bi = v; }           // later index wins a tie
     }
 #pragma unroll
@@ -95,8 +103,14 @@ k_answer(const float *__restrict__ w_ans, const float *__restrict__ u, const uin
     if (tid == 0) {
         for (int i = 1; i < kWaves; i++)
             if (red_f[i] > bv || (red_f[i] == bv && red_i[i] > bi)) { bv = red_f[i]; bi = red_i[i]; }
-        pred[q] = bi;
-        if (answer) {
+        if constexpr (TOPK) {
+            tk.idx[(size_t)q * tk.k] = bi;
+            tk.p[(size_t)q * tk.k] = bv;
+            lg[bi] = -1.0f;
+        } else {
+            pred[q] = bi;
+        }
+        if (!TOPK && answer) {
             const uint32_t y = answer[q];
             if (y < V) {
                 cost_acc += -lg[y];
@@ -104,8 +118,34 @@ k_answer(const float *__restrict__ w_ans, const float *__restrict__ u, const uin
             }
         }
     }
+    if constexpr (TOPK) {
+        for (uint32_t j = 1; j < tk.k; j++) {
+            __syncthreads();                // the last round's entry is marked, its red_f / red_i are read
+            bv = -INFINITY;
+            bi = 0;
+            for (uint32_t v = tid; v < V; v += kBlock) {
+                const float p = lg[v];
+                if (!(bv > p)) { bv = p; bi = v; }
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const float tv = __shfl_xor(bv, o);
+                const uint32_t ti = __shfl_xor(bi, o);
+                if (tv > bv || (tv == bv && ti > bi)) { bv = tv; bi = ti; }
+            }
+            if (lane == 0) { red_f[wave] = bv; red_i[wave] = bi; }
+            __syncthreads();
+            if (tid == 0) {
+                for (int i = 1; i < kWaves; i++)
+                    if (red_f[i] > bv || (red_f[i] == bv && red_i[i] > bi)) { bv = red_f[i]; bi = red_i[i]; }
+                tk.idx[(size_t)q * tk.k + j] = bi;
+                tk.p[(size_t)q * tk.k + j] = bv;
+                lg[bi] = -1.0f;
+            }
+        }
     }
-    if (tid == 0 && answer) {
+    }
+    if (!TOPK && tid == 0 && answer) {
         if (cost) atomicAdd(cost, cost_acc);
         if (match && match_acc) atomicAdd(match, match_acc);
     }
@@ -140,11 +180,28 @@ template <int CTRL> __device__ __forceinline__ double row_peer_f64(double v)
     return __builtin_bit_cast(double, (uint64_t)lo | ((uint64_t)hi << 32));
 }
 
-template <int LPQ, int VPT, int QB>
+// (value, index) arg-max over a query's LPQ lanes, ties to the highest index; every lane ends with the result (the ranked builds'
+// further rounds: the steps k_answer_small spells out for its first)
+template <int LPQ> __device__ __forceinline__ void row_argmax(float &bv, uint32_t &bi)
+{
+#define QM_STEP(C) { const float tv = row_peer_f32<C>(bv); const uint32_t ti = row_peer_u32<C>(bi); \
+                     if (tv > bv || (tv == bv && ti > bi)) { bv = tv; bi = ti; } }   /* ties go to the highest index */
+    QM_ROW_STEPS(QM_STEP)
+#undef QM_STEP
+#pragma unroll
+    for (int o = 16; o < LPQ; o <<= 1) {
+        const float tv = __shfl_xor(bv, o);
+        const uint32_t ti = __shfl_xor(bi, o);
+        if (tv > bv || (tv == bv && ti > bi)) { bv = tv; bi = ti; }
+    }
+}
+
+// TOPK: as in k_answer -- the rounds run on the lane's probabilities in registers, every lane of the group knows each winner
+template <int LPQ, int VPT, int QB, bool TOPK = false>
 __global__ void __launch_bounds__(kAnsBlock, 8)             // 64 registers: two workgroups per CU
 k_answer_small(const float *__restrict__ w_ans, const float *__restrict__ u, const uint32_t *__restrict__ answer,
                uint32_t *__restrict__ pred, float *__restrict__ probs, float *cost, uint32_t *match, uint32_t D,
-               uint32_t V, uint32_t softmax_base, uint32_t n_query)
+               uint32_t V, uint32_t softmax_base, uint32_t n_query, const AnsTopK<TOPK> tk)
 {
     static_assert(VPT % 2 == 0, "logits are handled in pairs");
     typedef float f2 __attribute__((ext_vector_type(2)));
@@ -233,7 +290,7 @@ k_answer_small(const float *__restrict__ w_ans, const float *__restrict__ u, con
             for (int k = 0; k < VPT; k++) {
                 p[k] = (softmax_base == QMANN_SOFTMAX_EXP) ? (float)((double)e[k] / total) : e[k] / (float)total;
                 if (live[k]) {
-                    if (probs && q_ok) probs[q * V + v0 + k] = p[k];
+                    if (!TOPK && probs && q_ok) probs[q * V + v0 + k] = p[k];
                     if (!(bv > p[k])) { bv = p[k]; bi = v0 + k; }               // later index wins a tie
                 }
             }
@@ -247,8 +304,24 @@ k_answer_small(const float *__restrict__ w_ans, const float *__restrict__ u, con
                 const uint32_t ti = __shfl_xor(bi, o);
                 if (tv > bv || (tv == bv && ti > bi)) { bv = tv; bi = ti; }
             }
-            if (sub == 0 && q_ok) pred[q] = bi;
-            if (answer) {
+            if constexpr (TOPK) {
+                for (uint32_t r = 0;;) {
+                    if (sub == 0 && q_ok) { tk.idx[q * tk.k + r] = bi; tk.p[q * tk.k + r] = bv; }
+                    if (++r == tk.k) break;
+                    const uint32_t taken = bi;
+                    bv = -INFINITY;
+                    bi = 0;
+#pragma unroll
+                    for (int k = 0; k < VPT; k++) {
+                        p[k] = (v0 + k == taken) ? -1.0f : p[k];
+                        if (live[k] && !(bv > p[k])) { bv = p[k]; bi = v0 + k; }
+                    }
+                    row_argmax<LPQ>(bv, bi);
+                }
+            } else {
+                if (sub == 0 && q_ok) pred[q] = bi;
+            }
+            if (!TOPK && answer) {
                 const uint32_t y = q_ok ? answer[q] : 0xFFFFFFFFu;
                 const uint32_t ys = y < V ? y : 0u;
                 float psel = p[0];
@@ -262,7 +335,7 @@ k_answer_small(const float *__restrict__ w_ans, const float *__restrict__ u, con
             }
         }
     }
-    if (answer) {
+    if (!TOPK && answer) {
 #pragma unroll
         for (int o = LPQ; o < kWave; o <<= 1) { cost_acc += __shfl_xor(cost_acc, o); match_acc += __shfl_xor(match_acc, o); }
         if (lane == 0) {
@@ -748,11 +821,14 @@ k_answer_i8_combine(const AnsPart *__restrict__ part, const float *__restrict__ 
 
 extern "C" {
 
+// tk: null, or the outputs of qmann_answer_topk_f32 -- the serial-order kernel of the shape in its top-k build (the bookkeeping
+// arguments are then unused)
 static int answer_f32_impl(const qmann_net *net, const float *w_ans, const float *u, const uint32_t *answer, uint32_t *pred,
-                           float *probs, float *cost, uint32_t *match, uint32_t n_query, void *stream, bool allow_fused)
+                           float *probs, float *cost, uint32_t *match, uint32_t n_query, void *stream, bool allow_fused,
+                           const AnsTopK<true> *tk = nullptr)
 {
     QmBatched qm_scope;
-    if (!net || !w_ans || !u || !pred) return QMANN_EINVAL;
+    if (!net || !w_ans || !u || (!pred && !tk)) return QMANN_EINVAL;
     const uint32_t D = net->dim_emb, V = net->dim_input;
     if (D == 0 || V == 0) return QMANN_EINVAL;
     const size_t lds = ((size_t)((D + 3) & ~3u) + V) * sizeof(float);
@@ -786,24 +862,28 @@ static int answer_f32_impl(const qmann_net *net, const float *w_ans, const float
     const size_t lds_small = ((size_t)D * lpq * vpt + (size_t)kAnsWaves * qpw * D) * sizeof(float);
     if (V <= 256u && lds_small <= 78 * 1024) {              // W^T fits LDS twice per CU
         const uint32_t need = (n_query + kAnsWaves * qpw - 1) / (kAnsWaves * qpw);
-        auto go = [&](auto kernel) {                        // persistent: two 16-wavefront workgroups per CU
-            qm_launch_persistent(kernel, need, QmPersistent{kAnsWaves, 8}, lds_small, st, w_ans, u, answer, pred, probs, cost, match, D, V, net->softmax_base, n_query);
+        auto go = [&](auto kernel, auto kernel_topk) {      // persistent: two 16-wavefront workgroups per CU
+            const QmPersistent wg{kAnsWaves, 8};
+            if (tk) qm_launch_persistent(kernel_topk, need, wg, lds_small, st, w_ans, u, answer, pred, probs, cost, match, D, V, net->softmax_base, n_query, *tk);
+            else qm_launch_persistent(kernel, need, wg, lds_small, st, w_ans, u, answer, pred, probs, cost, match, D, V, net->softmax_base, n_query, AnsTopK<false>{});
         };
         if (lpq == 64) {
-            go(k_answer_small<64, 4, 4>);                   // V in 129 .. 256
+            go(k_answer_small<64, 4, 4>, k_answer_small<64, 4, 4, true>);                   // V in 129 .. 256
         } else {
             switch (vpt) {
-            case 2: go(k_answer_small<16, 2, 2>); break;
-            case 4: go(k_answer_small<16, 4, 2>); break;
-            case 6: go(k_answer_small<16, 6, 2>); break;
-            default: go(k_answer_small<16, 8, 1>); break;
+            case 2: go(k_answer_small<16, 2, 2>, k_answer_small<16, 2, 2, true>); break;
+            case 4: go(k_answer_small<16, 4, 2>, k_answer_small<16, 4, 2, true>); break;
+            case 6: go(k_answer_small<16, 6, 2>, k_answer_small<16, 6, 2, true>); break;
+            default: go(k_answer_small<16, 8, 1>, k_answer_small<16, 8, 1, true>); break;
             }
         }
         QM_LAUNCH_CHECK();
         return qm_scope.rc();
     }
-    qm_launch(k_answer<false>, n_query < 8192u ? n_query : 8192u, kBlock, lds, st,
-              w_ans, u, answer, pred, probs, cost, match, D, V, net->softmax_base, n_query);
+    const uint32_t grid = n_query < 8192u ? n_query : 8192u;
+    if (tk) qm_launch(k_answer<false, true>, grid, kBlock, lds, st, w_ans, u, answer, pred, probs, cost, match, D, V, net->softmax_base, n_query, *tk);
+    else qm_launch(k_answer<false>, grid, kBlock, lds, st,
+              w_ans, u, answer, pred, probs, cost, match, D, V, net->softmax_base, n_query, AnsTopK<false>{});
     QM_LAUNCH_CHECK();
     return qm_scope.rc();
 }
@@ -818,6 +898,15 @@ int qmann_answer_f32_serial(const qmann_net *net, const float *w_ans, const floa
                             uint32_t *pred, float *probs, float *cost, uint32_t *match, uint32_t n_query, void *stream)
 {
     return answer_f32_impl(net, w_ans, u, answer, pred, probs, cost, match, n_query, stream, false);
+}
+
+int qmann_answer_topk_f32(const qmann_net *net, const float *w_ans, const float *u, uint32_t k, uint32_t *top_idx, float *top_p,
+                          uint32_t n_query, void *stream)
+{
+    if (!net || !w_ans || !u || !top_idx || !top_p) return QMANN_EINVAL;
+    if (k == 0 || k > QMANN_MAX_TOPK || k > net->dim_input) return QMANN_EINVAL;
+    const AnsTopK<true> tk{top_idx, top_p, k};
+    return answer_f32_impl(net, w_ans, u, nullptr, nullptr, nullptr, nullptr, nullptr, n_query, stream, false, &tk);
 }
 
 int qmann_answer_i8(const qmann_net *net, const int8_t *w_ans_i8, qmann_fmt w_fmt, const float *u, float *logits_ws,
@@ -869,7 +958,7 @@ int qmann_answer_i8(const qmann_net *net, const int8_t *w_ans_i8, qmann_fmt w_fm
         }))
         return QMANN_EUNSUPPORTED;
     qm_launch(k_answer<true>, n_query < 8192u ? n_query : 8192u, kBlock, lds, st,
-              logits_ws, nullptr, answer, pred, probs, cost, match, D, V, net->softmax_base, n_query);
+              logits_ws, nullptr, answer, pred, probs, cost, match, D, V, net->softmax_base, n_query, AnsTopK<false>{});
     QM_LAUNCH_CHECK();
     return qm_scope.rc();
 }

@@ -102,6 +102,7 @@ struct qmann_model {
     // attention mode, hence one of the two), allocated by that call and never inside an ask; split_bytes = 0: the mode is off
     void *split_ws = nullptr;
     size_t split_bytes = 0;
+    uint32_t last_n_query = 0;   // queries of the last forward that enqueued an answer layer (qmann_model_last_topk ranks m->u's rows)
     bool answer_exact = false;   // rt.h::qm_model_answer_exact: the float answer layer keeps the serial order of additions
 };
 
@@ -541,6 +542,7 @@ int qmann_model_forward_words(qmann_model *m, const uint16_t *story_words, uint3
     QmBatched qm_scope;
     if (!m) return QMANN_EINVAL;
     if (n_query == 0) return QMANN_OK;                  // (an empty batch needs no arrays)
+    m->last_n_query = 0;                                // (set again where this call succeeds)
     if ((!story_words && rows_total) || !question_words || !row_off || !pred) return QMANN_EINVAL;   // (every story may be empty)
     DeviceScope on(m->device);
     int rc = ensure(m, rows_total, n_query, use_planes(m, max_slots));
@@ -551,7 +553,9 @@ int qmann_model_forward_words(qmann_model *m, const uint16_t *story_words, uint3
         [&](void *s) { return qmann_embed_query_idx(&m->net, question_words, max_q_words, m->t_q, m->u0, n_query, s); });
     if (rc) return rc;
     rc = hops_and_answer(m, rows_total, row_off, max_slots, n_query, answer, pred, cost, match, stream, split_ws);
-    return rc ? rc : qm_scope.rc();
+    if (!rc) rc = qm_scope.rc();
+    if (!rc) m->last_n_query = n_query;
+    return rc;
 }
 
 int qmann_model_forward_shared_words(qmann_model *m, const uint16_t *story_words, uint32_t n_rows, uint32_t max_words,
@@ -561,6 +565,7 @@ int qmann_model_forward_shared_words(qmann_model *m, const uint16_t *story_words
     QmBatched qm_scope;
     if (!m) return QMANN_EINVAL;
     if (n_query == 0) return QMANN_OK;
+    m->last_n_query = 0;                                // (set again where this call succeeds)
     if (!story_words || !question_words || !pred) return QMANN_EINVAL;
     if (m->net.attention_mode != QMANN_ATT_FIXED) return QMANN_EUNSUPPORTED;     // (what qmann_hops_shared_i8 covers)
     if (n_rows == 0) return QMANN_EINVAL;
@@ -576,7 +581,9 @@ int qmann_model_forward_shared_words(qmann_model *m, const uint16_t *story_words
     rc = qmann_hops_shared_i8(&m->net, m->keys, m->vals, m->tied ? 0 : plane, n_rows, m->u0, m->u, nullptr, n_query, stream);
     if (rc) return rc;
     rc = qmann_answer_f32(&m->net, m->w_ans, m->u, answer, pred, nullptr, cost, match, n_query, stream);
-    return rc ? rc : qm_scope.rc();
+    if (!rc) rc = qm_scope.rc();
+    if (!rc) m->last_n_query = n_query;
+    return rc;
 }
 
 int qmann_model_memorize_words(qmann_model *m, const uint16_t *story_words, uint32_t n_rows, uint32_t max_words, void *stream)
@@ -619,8 +626,10 @@ int qmann_model_ask_words(qmann_model *m, const uint16_t *question_words, uint32
                           const uint32_t *answer, uint32_t *pred, float *cost, uint32_t *match, void *stream)
 {
     QmBatched qm_scope;
-    if (!m || m->mem_rows == 0) return QMANN_EINVAL;
+    if (!m) return QMANN_EINVAL;
+    if (m->mem_rows == 0) { m->last_n_query = 0; return QMANN_EINVAL; }
     if (n_query == 0) return QMANN_OK;
+    m->last_n_query = 0;                                // (set again where this call succeeds)
     if (!question_words || !pred) return QMANN_EINVAL;
     DeviceScope on(m->device);
     int rc = ensure_queries(m, n_query);
@@ -650,7 +659,9 @@ int qmann_model_ask_words(qmann_model *m, const uint16_t *question_words, uint32
         rc = qmann_hops_shared_i8(&m->net, m->mem_keys, m->mem_vals, plane, S, m->u0, m->u, nullptr, n_query, stream);
     if (rc) return rc;
     rc = (m->answer_exact ? qmann_answer_f32_serial : qmann_answer_f32)(&m->net, m->w_ans, m->u, answer, pred, nullptr, cost, match, n_query, stream);
-    return rc ? rc : qm_scope.rc();
+    if (!rc) rc = qm_scope.rc();
+    if (!rc) m->last_n_query = n_query;
+    return rc;
 }
 
 uint32_t qmann_model_memory_rows(const qmann_model *m) { return m ? m->mem_rows : 0u; }
@@ -682,6 +693,7 @@ int qmann_model_forward_bow(qmann_model *m, const float *story, uint32_t rows_to
     QmBatched qm_scope;
     if (!m) return QMANN_EINVAL;
     if (n_query == 0) return QMANN_OK;
+    m->last_n_query = 0;                                // (set again where this call succeeds)
     if ((!story && rows_total) || !question || !row_off || !pred) return QMANN_EINVAL;
     DeviceScope on(m->device);
     int rc = ensure(m, rows_total, n_query, use_planes(m, max_slots));
@@ -723,10 +735,21 @@ int qmann_model_forward_bow(qmann_model *m, const float *story, uint32_t rows_to
         });
     if (rc) return rc;
     rc = hops_and_answer(m, rows_total, row_off, max_slots, n_query, answer, pred, cost, match, stream, split_ws);
-    return rc ? rc : qm_scope.rc();
+    if (!rc) rc = qm_scope.rc();
+    if (!rc) m->last_n_query = n_query;
+    return rc;
 }
 
 const float *qmann_model_last_u(const qmann_model *m) { return m ? m->u : nullptr; }
+
+uint32_t qmann_model_last_n_query(const qmann_model *m) { return m ? m->last_n_query : 0u; }
+
+int qmann_model_last_topk(qmann_model *m, uint32_t k, uint32_t *top_idx, float *top_p, void *stream)
+{
+    if (!m || m->last_n_query == 0 || !m->u) return QMANN_EINVAL;
+    DeviceScope on(m->device);
+    return qmann_answer_topk_f32(&m->net, m->w_ans, m->u, k, top_idx, top_p, m->last_n_query, stream);
+}
 
 }  // extern "C"
 

@@ -416,6 +416,16 @@ class QNet:
                      _ptr(probs), _ptr(cost), _ptr(match), B, self._s()), "qmann_answer_f32")
         return pred, probs, cost, match
 
+    def answer_topk(self, u, k):
+        """qmann_answer_topk_f32: per row of u the k most probable answers of the serial-order layer, (top_idx int32 [B, k],
+        top_p float32 [B, k]), larger probability first, equal probabilities: higher index first"""
+        B = u.shape[0]
+        top_idx = torch.empty((B, k), dtype=torch.int32, device=self.dev)
+        top_p = torch.empty((B, k), dtype=torch.float32, device=self.dev)
+        abi.check(abi.lib.qmann_answer_topk_f32(C.byref(self.net), _ptr(self.w_ans), _ptr(u), k, _ptr(top_idx), _ptr(top_p), B,
+                                                self._s()), "qmann_answer_topk_f32")
+        return top_idx, top_p
+
     def answer_i8(self, u, w_ans_i8, w_fmt, answer=None, want_probs=False):
         """Answer layer on the int8 matrix cores; w_ans_i8 [V][Dp] two's-complement codes of Q(w_fmt)."""
         B = u.shape[0]
@@ -507,6 +517,15 @@ class HostModel:
         host = np.empty((B, self.D), np.float32)
         abi.lib.cuda_copy_dev2host(host.ctypes.data_as(C.c_void_p), C.c_void_p(p), B * self.D)   # boundary B's own D2H verb
         return torch.from_numpy(host).to(self.dev)
+
+    def last_topk(self, k):
+        """qmann_model_last_topk: the k most probable answers of every question of the last batch, (top_idx int32 [B, k],
+        top_p float32 [B, k]) as QNet.answer_topk gives them for last_u"""
+        B = int(abi.lib.qmann_model_last_n_query(self.h))         # (0: the library refuses, nothing is written)
+        top_idx = torch.empty((B, k), dtype=torch.int32, device=self.dev)
+        top_p = torch.empty((B, k), dtype=torch.float32, device=self.dev)
+        abi.check(abi.lib.qmann_model_last_topk(self.h, k, _ptr(top_idx), _ptr(top_p), self._s()), "qmann_model_last_topk")
+        return top_idx, top_p
 
     def forward_words(self, story_words, question_words, row_off, max_slots, answer=None):
         B = question_words.shape[0]

@@ -18,5 +18,6 @@ for side in A B; do
 done
 rc=0
 norm() { grep -v '^\s*\.file\|^\s*\.ident\|\.loc\b' $1 | sed 's/__hip_cuid_[0-9a-f]*/__hip_cuid_X/g'; }    # (the compilation-unit id hashes the whole source text)
-for s in $T/A/*.s; do b=$(basename $s); if cmp -s <(norm $s) <(norm $T/B/$b); then echo "same      $b"; else echo "DIFFERENT $b"; rc=1; fi; done
-rm -rf $T; exit $rc
+# (a DIFFERENT unit is listed kernel by kernel; KEEP=1 leaves the .s files of both sides in place for a closer look)
+for s in $T/A/*.s; do b=$(basename $s); if cmp -s <(norm $s) <(norm $T/B/$b); then echo "same      $b"; else echo "DIFFERENT $b"; rc=1; python3 $R/tools/device_asm_kernels.py $s $T/B/$b | sed 's/^/    /'; fi; done
+if [ -n "$KEEP" ]; then echo "kept: $T/A $T/B"; else rm -rf $T; fi; exit $rc
