@@ -181,6 +181,34 @@ int qmann_hops_shared_split_i8(const qmann_net *net, const int8_t *keys, const i
                                uint32_t n_slots, const float *u0, float *u_out, const qmann_taps *taps, uint32_t n_query,
                                uint32_t n_slices, void *ws, size_t ws_bytes, void *stream);
 
+/* Attended slots: qmann_hops_shared_i8 / qmann_hops_shared_split_i8 that also return, per query and hop, the k memory rows the
+ * hop weighted most and their weights -- the supporting facts -- without a [n_hop][n_query][n_slots] array anywhere.
+ *   top_slot [n_query][n_hop][k] uint32, top_p [n_query][n_hop][k] float, device memory; 1 <= k <= QMANN_MAX_TOP_SLOTS.
+ * In terms of what qmann_hops_shared_i8 writes to taps.probs for the same arguments: row (q, h) lists the k slots of
+ * probs[h][q][:] that come first in the order "larger probability first, equal probabilities: lower slot index first", and
+ * top_p[q][h][j] is bit-equal to probs[h][q][top_slot[q][h][j]].  The order is over the probability VALUES: slots whose scores
+ * differ tie where their probabilities are equal floats (the zero region of exp_plan, underflow to 0, att_scale = 0), and a
+ * negative att_scale needs no rule of its own.  Where k > n_slots the entries past n_slots hold slot 0xFFFFFFFF and p 0.0f.
+ * u_out is the base call's bit for bit, and every qmann_net field the base call honours is honoured (the three softmax bases,
+ * the shift-based normaliser, en_att_scale, ReLU, binary u, tied hops with hop_stride = 0, per-hop formats).  There is no taps
+ * argument: a host that wants taps calls the base functions.
+ * The selection runs inside the base call's kernels behind each query's hop (csrc/hops_attended.h), from the score histogram and
+ * the score bytes the hop already holds; LDS per query, tiles and caps are the base call's.  The split call takes the SAME
+ * workspace and qmann_hops_shared_split_ws_bytes figure as qmann_hops_shared_split_i8.  Both are ordered steps on `stream` with
+ * the node counts of their base calls (1; 1 + 2 n_hop), no allocation, no library scratch, no second stream: they can be captured
+ * in a graph.
+ * Nothing is launched, no output is touched and the code returned is: every refusal of the respective base call, unchanged and
+ * FIRST (a call with a fault of the base call and a fault below returns the base call's code; n_query = 0 is QMANN_OK whatever
+ * k); then QMANN_EINVAL for k = 0, k > QMANN_MAX_TOP_SLOTS, a null top_slot or top_p.  k > n_slots is no error. */
+#define QMANN_MAX_TOP_SLOTS 16
+int qmann_hops_shared_top_i8(const qmann_net *net, const int8_t *keys, const int8_t *vals, size_t hop_stride,
+                             uint32_t n_slots, const float *u0, float *u_out, uint32_t k,
+                             uint32_t *top_slot, float *top_p, uint32_t n_query, void *stream);
+int qmann_hops_shared_split_top_i8(const qmann_net *net, const int8_t *keys, const int8_t *vals, size_t hop_stride,
+                                   uint32_t n_slots, const float *u0, float *u_out, uint32_t k,
+                                   uint32_t *top_slot, float *top_p, uint32_t n_query, uint32_t n_slices,
+                                   void *ws, size_t ws_bytes, void *stream);
+
 /* Packed binary codes for the Hamming forms: sign-magnitude bytes [rows][Dp] -> bit planes
  * uint64 [rows][Dp/64][num_bit] (plane 0 = sign bits, plane i = magnitude bit 7-i; bit b of a word
  * is column 64.g + b).  num_bit in 1..8.  sm_codes 16-byte aligned, planes 8-byte aligned (QMANN_EINVAL otherwise). */

@@ -16,6 +16,7 @@ if not LIB_PATH.exists():
 lib = C.CDLL(str(LIB_PATH))
 
 QMANN_MAX_HOP = 8
+QMANN_MAX_TOP_SLOTS = 16           # qmann_batch.h: attended slots per query and hop
 ATT_FLOAT, ATT_FIXED, ATT_APPX, ATT_HAMMING_V0, ATT_HAMMING_V1, ATT_SIGN = 1, 2, 3, 10, 11, 12
 SOFTMAX_EXP, SOFTMAX_POW2 = 0, 1
 CODE_TWOS, CODE_SIGNMAG = 0, 1
@@ -170,6 +171,10 @@ _proto("qmann_hops_shared_split_ws_bytes", C.c_size_t, [C.POINTER(Net), C.c_uint
 _proto("qmann_hops_shared_split_slices", C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32])
 _proto("qmann_hops_shared_split_i8", C.c_int, [C.POINTER(Net), _vp, _vp, C.c_size_t, C.c_uint32, _vp, _vp,
                                                C.POINTER(Taps), C.c_uint32, C.c_uint32, _vp, C.c_size_t, _vp])
+_proto("qmann_hops_shared_top_i8", C.c_int, [C.POINTER(Net), _vp, _vp, C.c_size_t, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp,
+                                             C.c_uint32, _vp])
+_proto("qmann_hops_shared_split_top_i8", C.c_int, [C.POINTER(Net), _vp, _vp, C.c_size_t, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp,
+                                                   C.c_uint32, C.c_uint32, _vp, C.c_size_t, _vp])
 _proto("qmann_hops_shared_packed", C.c_int, [C.POINTER(Net), _vp, C.c_size_t, _vp, C.c_size_t, C.c_uint32, _vp, _vp,
                                              C.POINTER(Taps), C.c_uint32, _vp])
 _proto("qmann_hops_shared_split_packed_ws_bytes", C.c_size_t, [C.POINTER(Net), C.c_uint32, C.c_uint32])
@@ -219,6 +224,7 @@ _proto("qmann_model_forward_shared_words", C.c_int, [_vp, _vp, C.c_uint32, C.c_u
                                                      _vp, _vp, _vp, _vp, _vp])
 _proto("qmann_model_memorize_words", C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _vp])
 _proto("qmann_model_ask_words", C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, _vp])
+_proto("qmann_model_ask_words_top", C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp])
 _proto("qmann_model_memory_rows", C.c_uint32, [_vp])
 _proto("qmann_model_forward_bow", C.c_int, [_vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, _vp])
 _proto("qmann_model_enable_split_asks", C.c_int, [_vp, C.c_size_t, _vp])

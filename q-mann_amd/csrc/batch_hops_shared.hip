@@ -14,15 +14,17 @@
 //      hops_common.h, QT times): histogram softmax, survivor search, sparse read-out, linear map, hop update.
 //
 // A last tile with fewer than QT queries scans with a live query's constants in the spare places and drops their sums.
-#include "hops_shared.h"
+#include "hops_attended.h"
 
 namespace {
 
 // (kSharedLdsLimit, QueryLds and scan_rows_shared: hops_shared.h, shared with batch_hops_shared_split.hip)
 // per_q: bytes of LDS per query (qmann_hops_lds_bytes(n_slots)); a.max_slots = n_slots >= 1
-template <int LPR, int QT, bool W7>
+// TOP (qmann_hops_shared_top_i8): behind every query's hop its k most attended slots go to tp.slot / tp.p (hops_attended.h).
+// The TOP builds are instantiations of their own: the others take an EMPTY last argument and keep their device code.
+template <int LPR, int QT, bool W7, bool TOP = false>
 __global__ void __launch_bounds__(kBlock, 1)
-k_hops_shared(const HopArgs a, const uint32_t n_query, const uint32_t per_q)
+k_hops_shared(const HopArgs a, const uint32_t n_query, const uint32_t per_q, const AttTop<TOP> tp)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr uint32_t Dp = LPR * 16, UN = kUnrollDefault;
@@ -87,6 +89,8 @@ k_hops_shared(const HopArgs a, const uint32_t n_query, const uint32_t per_q)
                                                            L.live_kp, L.misc, L.red, tid, lane, wave, (uint32_t)kBlock, (uint32_t)kWaves);
             auto kp_of_row = [&](uint32_t r) { return (int)L.kplut[(int)L.sc[r] + 127]; };
             finish_hop<Dp>(a, q0 + t, h, 0u, S, n_live, L.live_row, L.live_kp, kp_of_row, L.ku, L.u_f, L.o_f, tid);
+            if constexpr (TOP)
+                attended_select(tp, (size_t)(q0 + t) * a.n_hop + h, S, L.hist, L.ptab, L.sc, L.live_row, L.live_kp, L.misc, L.red, tid, lane, wave);
         }
     }
     for (uint32_t t = 0; t < nq; t++) {
@@ -129,8 +133,10 @@ uint32_t qmann_hops_shared_tile(uint32_t n_slots, uint32_t n_query)
     return choose_qt(n_slots, n_query);
 }
 
-int qmann_hops_shared_i8(const qmann_net *net, const int8_t *keys, const int8_t *vals, size_t hop_stride, uint32_t n_slots,
-                         const float *u0, float *u_out, const qmann_taps *taps, uint32_t n_query, void *stream)
+// tp: null, or the outputs of qmann_hops_shared_top_i8 -- the same launch in its TOP build
+static int hops_shared_impl(const qmann_net *net, const int8_t *keys, const int8_t *vals, size_t hop_stride, uint32_t n_slots,
+                            const float *u0, float *u_out, const qmann_taps *taps, uint32_t n_query, void *stream,
+                            const AttTop<true> *tp)
 {
     QmBatched qm_scope;
     static const uint32_t no_row_off = 0;                     // this call has no row_off: the shared checks want a non-null one
@@ -144,19 +150,38 @@ int qmann_hops_shared_i8(const qmann_net *net, const int8_t *keys, const int8_t 
     if (qmann_hops_shared_lds_bytes(n_slots, 1) > kSharedLdsLimit) return QMANN_ERANGE;
     if (n_query == 0) return QMANN_OK;
     if (qm_too_many_queries(n_query)) return QMANN_ERANGE;
+    if (tp && !att_top_args_ok(tp->k, tp->slot, tp->p)) return QMANN_EINVAL;     // behind every refusal of the base call
 
     const bool w7 = !qm_tuning().no_w7 && all_w7(a, kW7Att);
     const uint32_t qt = choose_qt(n_slots, n_query), per_q = (uint32_t)qmann_hops_lds_bytes(n_slots);
     qm_dispatch<4, 8, 16>(net->dim_emb_pad / 16, [&](auto lpr) {
         qm_dispatch<1, 2, 4, 8>(qt, [&](auto t) {
             qm_dispatch<false, true>(w7, [&](auto w) {
-                qm_launch(k_hops_shared<decltype(lpr)::value, decltype(t)::value, decltype(w)::value>, qm_cdiv(n_query, qt), dim3(kBlock),
-                          (size_t)qt * per_q, (hipStream_t)stream, a, n_query, per_q);
+                constexpr int LPR = decltype(lpr)::value, QT = decltype(t)::value;
+                constexpr bool W7 = decltype(w)::value;
+                if (tp) qm_launch(k_hops_shared<LPR, QT, W7, true>, qm_cdiv(n_query, qt), dim3(kBlock), (size_t)qt * per_q,
+                                  (hipStream_t)stream, a, n_query, per_q, *tp);
+                else qm_launch(k_hops_shared<LPR, QT, W7>, qm_cdiv(n_query, qt), dim3(kBlock),
+                          (size_t)qt * per_q, (hipStream_t)stream, a, n_query, per_q, AttTop<false>{});
             });
         });
     });
     QM_LAUNCH_CHECK();
     return qm_scope.rc();
+}
+
+int qmann_hops_shared_i8(const qmann_net *net, const int8_t *keys, const int8_t *vals, size_t hop_stride, uint32_t n_slots,
+                         const float *u0, float *u_out, const qmann_taps *taps, uint32_t n_query, void *stream)
+{
+    return hops_shared_impl(net, keys, vals, hop_stride, n_slots, u0, u_out, taps, n_query, stream, nullptr);
+}
+
+int qmann_hops_shared_top_i8(const qmann_net *net, const int8_t *keys, const int8_t *vals, size_t hop_stride, uint32_t n_slots,
+                             const float *u0, float *u_out, uint32_t k, uint32_t *top_slot, float *top_p, uint32_t n_query,
+                             void *stream)
+{
+    const AttTop<true> tp{top_slot, top_p, k};
+    return hops_shared_impl(net, keys, vals, hop_stride, n_slots, u0, u_out, nullptr, n_query, stream, &tp);
 }
 
 }  // extern "C"

@@ -23,7 +23,7 @@
 // of a step lie within one 64-row stretch).  Staging a slice in LDS and storing 16 bytes at a time has NOT been measured.
 // The 2^x and exp_plan bases keep their serial float total in slot order: block_serial_total_f32 then walks the score bytes in
 // the workspace (global memory, L2 hits) instead of LDS -- right, but not fast at length.
-#include "hops_shared.h"
+#include "hops_attended.h"
 
 namespace {
 
@@ -142,9 +142,11 @@ k_shared_split_scan(const HopArgs a, const uint32_t n_query, const uint32_t h, c
     }
 }
 
-template <uint32_t Dp>
+// TOP (qmann_hops_shared_split_top_i8): the query's k most attended slots of this hop go to tp.slot / tp.p (hops_attended.h,
+// the score bytes read from the workspace); the other builds take an EMPTY last argument and keep their device code.
+template <uint32_t Dp, bool TOP = false>
 __global__ void __launch_bounds__(kBlock)
-k_shared_split_finish(const HopArgs a, const uint32_t n_query, const uint32_t h, const SplitWs w)
+k_shared_split_finish(const HopArgs a, const uint32_t n_query, const uint32_t h, const SplitWs w, const AttTop<TOP> tp)
 {
     __shared__ __attribute__((aligned(16))) unsigned char smem[kOffScores];
     const uint32_t tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
@@ -170,6 +172,8 @@ k_shared_split_finish(const HopArgs a, const uint32_t n_query, const uint32_t h,
                                                    L.live_kp, L.misc, L.red, tid, lane, wave, (uint32_t)kBlock, (uint32_t)kWaves);
     auto kp_of_row = [&](uint32_t r) { return (int)L.kplut[(int)sc[r] + 127]; };
     finish_hop<Dp>(a, q, h, 0u, S, n_live, L.live_row, L.live_kp, kp_of_row, L.ku, L.u_f, L.o_f, tid);
+    if constexpr (TOP)
+        attended_select(tp, (size_t)q * a.n_hop + h, S, L.hist, L.ptab, sc, L.live_row, L.live_kp, L.misc, L.red, tid, lane, wave);
 
     if (h + 1 < a.n_hop) {
         for (uint32_t c = tid; c < D; c += kBlock) u_g[c] = L.u_f[c];
@@ -210,9 +214,10 @@ uint32_t qmann_hops_shared_split_slices(uint32_t n_slots, uint32_t dim_emb_pad, 
     return w.n_slices;
 }
 
-int qmann_hops_shared_split_i8(const qmann_net *net, const int8_t *keys, const int8_t *vals, size_t hop_stride, uint32_t n_slots,
-                               const float *u0, float *u_out, const qmann_taps *taps, uint32_t n_query, uint32_t n_slices, void *ws,
-                               size_t ws_bytes, void *stream)
+// tp: null, or the outputs of qmann_hops_shared_split_top_i8 -- the same launches, the finish kernel in its TOP build
+static int hops_shared_split_impl(const qmann_net *net, const int8_t *keys, const int8_t *vals, size_t hop_stride, uint32_t n_slots,
+                                  const float *u0, float *u_out, const qmann_taps *taps, uint32_t n_query, uint32_t n_slices,
+                                  void *ws, size_t ws_bytes, void *stream, const AttTop<true> *tp)
 {
     QmBatched qm_scope;
     static const uint32_t no_row_off = 0;                     // this call has no row_off: the shared checks want a non-null one
@@ -227,6 +232,7 @@ int qmann_hops_shared_split_i8(const qmann_net *net, const int8_t *keys, const i
     if (n_query == 0) return QMANN_OK;
     if (qm_too_many_queries(n_query)) return QMANN_ERANGE;
     if (ws_bytes < qmann_hops_shared_split_ws_bytes(net, n_slots, n_query)) return QMANN_EINVAL;
+    if (tp && !att_top_args_ok(tp->k, tp->slot, tp->p)) return QMANN_EINVAL;     // behind every refusal of the base call
 
     SplitWs w{};
     w.pitch = split_pitch(n_slots);
@@ -248,11 +254,27 @@ int qmann_hops_shared_split_i8(const qmann_net *net, const int8_t *keys, const i
                               dim3(kBlock), 0, st, a, n_query, h, w);
                 });
             });
-            qm_launch(k_shared_split_finish<(uint32_t)LPR * 16u>, n_query, dim3(kBlock), 0, st, a, n_query, h, w);
+            if (tp) qm_launch(k_shared_split_finish<(uint32_t)LPR * 16u, true>, n_query, dim3(kBlock), 0, st, a, n_query, h, w, *tp);
+            else qm_launch(k_shared_split_finish<(uint32_t)LPR * 16u>, n_query, dim3(kBlock), 0, st, a, n_query, h, w, AttTop<false>{});
         });
     }
     QM_LAUNCH_CHECK();
     return qm_scope.rc();
+}
+
+int qmann_hops_shared_split_i8(const qmann_net *net, const int8_t *keys, const int8_t *vals, size_t hop_stride, uint32_t n_slots,
+                               const float *u0, float *u_out, const qmann_taps *taps, uint32_t n_query, uint32_t n_slices, void *ws,
+                               size_t ws_bytes, void *stream)
+{
+    return hops_shared_split_impl(net, keys, vals, hop_stride, n_slots, u0, u_out, taps, n_query, n_slices, ws, ws_bytes, stream, nullptr);
+}
+
+int qmann_hops_shared_split_top_i8(const qmann_net *net, const int8_t *keys, const int8_t *vals, size_t hop_stride, uint32_t n_slots,
+                                   const float *u0, float *u_out, uint32_t k, uint32_t *top_slot, float *top_p, uint32_t n_query,
+                                   uint32_t n_slices, void *ws, size_t ws_bytes, void *stream)
+{
+    const AttTop<true> tp{top_slot, top_p, k};
+    return hops_shared_split_impl(net, keys, vals, hop_stride, n_slots, u0, u_out, nullptr, n_query, n_slices, ws, ws_bytes, stream, &tp);
 }
 
 }  // extern "C"

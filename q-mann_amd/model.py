@@ -140,6 +140,13 @@ def _zero_cost_and_match(dev):
     return acc[:1].view(torch.float32), acc[1:]
 
 
+def _top_out(dev, B, H, k):
+    """outputs of the attended-slots calls: top_slot int32 [B][H][k] (0xFFFFFFFF reads -1), top_p float32 [B][H][k]"""
+    if not 1 <= k <= abi.QMANN_MAX_TOP_SLOTS:
+        raise ValueError(f"k = {k}: the attended-slots calls take 1 .. {abi.QMANN_MAX_TOP_SLOTS}")
+    return (torch.empty((B, H, k), dtype=torch.int32, device=dev), torch.empty((B, H, k), dtype=torch.float32, device=dev))
+
+
 class QNet:
     """cfg: the dict shape used by oracle/pyoracle.py (n_hop, dim_emb, dim_input, attention_mode,
     softmax_variant (0 e^x / 1 2^x), en_lin_map, fmt, fmt_w, fmt_att, fmt_bin).
@@ -311,6 +318,38 @@ class QNet:
                                                      self._s()), "qmann_hops_shared_split_i8")
         self._split_ws = ws                                                       # alive until the next call: the launch is asynchronous
         return (u_out, tobj) if taps else u_out
+
+    def hops_shared_top(self, keys, vals, n_slots, u0, k):
+        """qmann_hops_shared_top_i8: hops_shared plus, per query and hop, the k most attended slots and their probabilities:
+        (u_out, top_slot int32 [B][H][k], top_p float32 [B][H][k]), larger probability first, equal probabilities: lower slot
+        first; entries past n_slots are slot -1 (0xFFFFFFFF), p 0.  Arguments as hops_shared."""
+        B = u0.shape[0]
+        assert keys.shape in ((self.H, n_slots, self.Dp), (1, n_slots, self.Dp)) and vals.shape == keys.shape
+        assert keys.is_contiguous() and vals.is_contiguous()
+        u_out = torch.empty_like(u0)
+        top_slot, top_p = _top_out(self.dev, B, self.H, k)
+        hop_stride = n_slots * self.Dp if keys.shape[0] == self.H else 0          # one plane for several hops: tied
+        abi.check(abi.lib.qmann_hops_shared_top_i8(C.byref(self.net), _ptr(keys), _ptr(vals), hop_stride, n_slots, _ptr(u0),
+                                                   _ptr(u_out), k, _ptr(top_slot), _ptr(top_p), B, self._s()),
+                  "qmann_hops_shared_top_i8")
+        return u_out, top_slot, top_p
+
+    def hops_shared_split_top(self, keys, vals, n_slots, u0, k, n_slices=0):
+        """qmann_hops_shared_split_top_i8: hops_shared_top with the slots cut into n_slices slices (0: the library's choice);
+        the workspace is allocated here, of the size hops_shared_split takes.  Results as hops_shared_top."""
+        B = u0.shape[0]
+        assert keys.shape in ((self.H, n_slots, self.Dp), (1, n_slots, self.Dp)) and vals.shape == keys.shape
+        assert keys.is_contiguous() and vals.is_contiguous()
+        u_out = torch.empty_like(u0)
+        top_slot, top_p = _top_out(self.dev, B, self.H, k)
+        nbytes = int(abi.lib.qmann_hops_shared_split_ws_bytes(C.byref(self.net), n_slots, B))
+        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=self.dev)       # (torch allocations are 16-byte aligned)
+        hop_stride = n_slots * self.Dp if keys.shape[0] == self.H else 0
+        abi.check(abi.lib.qmann_hops_shared_split_top_i8(C.byref(self.net), _ptr(keys), _ptr(vals), hop_stride, n_slots, _ptr(u0),
+                                                         _ptr(u_out), k, _ptr(top_slot), _ptr(top_p), B, n_slices, _ptr(ws),
+                                                         nbytes, self._s()), "qmann_hops_shared_split_top_i8")
+        self._split_ws = ws                                                       # alive until the next call: the launch is asynchronous
+        return u_out, top_slot, top_p
 
     def pack_planes(self, sm_codes: torch.Tensor, num_bit: int) -> torch.Tensor:
         """sign-magnitude int8 [..., rows, Dp] -> packed bit planes int64 [..., rows, Dp/64, num_bit]."""
@@ -573,6 +612,17 @@ class HostModel:
         abi.check(abi.lib.qmann_model_ask_words(self.h, _ptr(question_words), question_words.shape[1], B, _ptr(answer),
                                                 _ptr(pred), _ptr(cost), _ptr(match), self._s()), "qmann_model_ask_words")
         return pred, cost, match
+
+    def ask_words_top(self, question_words, k, answer=None):
+        """qmann_model_ask_words_top: ask_words plus the attended slots of every question and hop: (pred, cost, match,
+        top_slot int32 [B][H][k], top_p float32 [B][H][k]) -- rows of the memorised story, as QNet.hops_shared_top gives them"""
+        B = question_words.shape[0]
+        pred, cost, match = self._out(B, answer)
+        top_slot, top_p = _top_out(self.dev, B, self.cfg["n_hop"], k)
+        abi.check(abi.lib.qmann_model_ask_words_top(self.h, _ptr(question_words), question_words.shape[1], B, _ptr(answer),
+                                                    _ptr(pred), _ptr(cost), _ptr(match), k, _ptr(top_slot), _ptr(top_p),
+                                                    self._s()), "qmann_model_ask_words_top")
+        return pred, cost, match, top_slot, top_p
 
     def forward_bow(self, story, question, row_off, max_slots, answer=None):
         B = question.shape[0]

@@ -4,7 +4,8 @@ it reports DIFFERENT.)
     python3 tools/device_asm_kernels.py A.s B.s [--rename-b PATTERN REPLACEMENT]
 
 A kernel is the text from its label to its .Lfunc_end; the ordinal of the function in the file, which the assembler's local
-labels and loop comments carry (.LBB12_3, BB12_3, .Lfunc_end12), is taken out, so a kernel that merely moved compares equal.
+labels and loop comments carry (.LBB12_3, BB12_3, .Lfunc_end12), is taken out, so a kernel that merely moved compares equal;
+runs of blanks count as one (the comment behind a label is padded by the label's length, which carries the ordinal's digits).
 --rename-b rewrites B's text first (a regular expression), for a kernel whose NAME changed: e.g. a template that gained a
 defaulted argument.  Prints one line per kernel: same / DIFFERENT (with the differing lines counted) / only in A / only in B;
 exit status 1 when a kernel of A is missing from B or differs."""
@@ -27,6 +28,7 @@ def kernels(text):
             continue
         if cur is not None:
             line = re.sub(r"\.Lfunc_end\d+", ".Lfunc_end", re.sub(r"BB\d+_", "BB_", line))
+            line = re.sub(r"[ \t]+", " ", line)
             out[cur].append(line)
             if line.startswith(".Lfunc_end"):
                 cur = None
