@@ -191,7 +191,8 @@ int qmann_hops_shared_split_i8(const qmann_net *net, const int8_t *keys, const i
  * negative att_scale needs no rule of its own.  Where k > n_slots the entries past n_slots hold slot 0xFFFFFFFF and p 0.0f.
  * u_out is the base call's bit for bit, and every qmann_net field the base call honours is honoured (the three softmax bases,
  * the shift-based normaliser, en_att_scale, ReLU, binary u, tied hops with hop_stride = 0, per-hop formats).  There is no taps
- * argument: a host that wants taps calls the base functions.
+ * argument: a host that wants taps calls the base functions.  (Hamming V0 / V1 on packed codes: qmann_hops_shared_top_packed /
+ * qmann_hops_shared_split_top_packed below.)
  * The selection runs inside the base call's kernels behind each query's hop (csrc/hops_attended.h), from the score histogram and
  * the score bytes the hop already holds; LDS per query, tiles and caps are the base call's.  The split call takes the SAME
  * workspace and qmann_hops_shared_split_ws_bytes figure as qmann_hops_shared_split_i8.  Both are ordered steps on `stream` with
@@ -269,6 +270,35 @@ int qmann_hops_shared_split_packed(const qmann_net *net, const uint64_t *key_pla
                                    const int8_t *vals, size_t val_hop_stride, uint32_t n_slots, const float *u0,
                                    float *u_out, const qmann_taps *taps, uint32_t n_query, uint32_t n_slices, void *ws,
                                    size_t ws_bytes, void *stream);
+
+/* Attended slots for the packed Hamming forms: qmann_hops_shared_packed / qmann_hops_shared_split_packed that also return, per
+ * query and hop, the k memory rows the hop weighted most and their weights, as qmann_hops_shared_top_i8 does for the fixed-point
+ * attention -- without a [n_hop][n_query][n_slots] array anywhere.
+ *   top_slot [n_query][n_hop][k] uint32, top_p [n_query][n_hop][k] float, device memory; 1 <= k <= QMANN_MAX_TOP_SLOTS.
+ * In terms of what qmann_hops_shared_packed writes to taps.probs for the same arguments: row (q, h) lists the k slots of
+ * probs[h][q][:] that come first in the order "larger probability first, equal probabilities: lower slot index first", and
+ * top_p[q][h][j] is bit-equal to probs[h][q][top_slot[q][h][j]].  The order is over the probability VALUES: slots whose scores
+ * differ tie where their probabilities are equal floats, a NaN probability ranks below every number, and a negative att_scale
+ * needs no rule of its own.  Where k > n_slots the entries past n_slots hold slot 0xFFFFFFFF and p 0.0f.
+ * u_out is the base call's bit for bit, and every qmann_net field the base call honours is honoured (the three softmax bases,
+ * the shift-based normaliser, att_scale of either sign, ReLU, binary u, tied hops with both strides 0, the per-hop formats of
+ * the mixed quantisation, num_bit in {1, 2, 4, 8}).  There is no taps argument: a host that wants taps calls the base functions.
+ * The selection runs inside the base call's kernels (csrc/hops_attended_ham.h).  V0: from the bins and the probability per bin
+ * the histogram softmax leaves behind.  V1: from the int16 scores and the softmax's own maximum and total, ALL slots ranked,
+ * those below the threshold shortcut of the survivor search included.  LDS per query, tiles, caps and the split workspace are
+ * the base call's: the split call takes the SAME workspace and qmann_hops_shared_split_packed_ws_bytes figure as
+ * qmann_hops_shared_split_packed.  Both are ordered steps on `stream` with the node counts of their base calls (1; at most
+ * 1 + 2 n_hop), no allocation, no library scratch, no second stream: they can be captured in a graph.
+ * Nothing is launched, no output is touched and the code returned is: every refusal of the respective base call, unchanged and
+ * FIRST (a call with a fault of the base call and a fault below returns the base call's code; n_query = 0 is QMANN_OK whatever
+ * k); then QMANN_EINVAL for k = 0, k > QMANN_MAX_TOP_SLOTS, a null top_slot or top_p.  k > n_slots is no error. */
+int qmann_hops_shared_top_packed(const qmann_net *net, const uint64_t *key_planes, size_t key_hop_stride,
+                                 const int8_t *vals, size_t val_hop_stride, uint32_t n_slots, const float *u0,
+                                 float *u_out, uint32_t k, uint32_t *top_slot, float *top_p, uint32_t n_query, void *stream);
+int qmann_hops_shared_split_top_packed(const qmann_net *net, const uint64_t *key_planes, size_t key_hop_stride,
+                                       const int8_t *vals, size_t val_hop_stride, uint32_t n_slots, const float *u0,
+                                       float *u_out, uint32_t k, uint32_t *top_slot, float *top_p, uint32_t n_query,
+                                       uint32_t n_slices, void *ws, size_t ws_bytes, void *stream);
 
 /* Answer layer for a batch: logits = W_ans . u (float, ds_ans is always float: MemN2N.c:902-906),
  * softmax over V, arg-max with ties to the highest index, and -- when `answer` is given -- the

@@ -132,14 +132,27 @@ uint32_t qmann_model_memory_rows(const qmann_model *m);
  * call in chunks of floor(budget / share) questions, each chunk writing its own block of rows.  pred, cost, match,
  * qmann_model_last_u and what qmann_model_last_topk ranks are those of qmann_model_ask_words; it allocates nothing once the
  * question workspace has its size, so it can be captured in a graph and replayed.
- * QMANN_ATT_FIXED models only: a Hamming V0 / V1 model returns QMANN_EUNSUPPORTED (the packed forms are a follow-up: their
- * softmax is per slot (V1) or over up to 2 049 bins (V0), a different selection).  What qmann_model_ask_words refuses or
- * answers without work is answered FIRST and as there (nothing memorised: QMANN_EINVAL; n_query = 0: QMANN_OK whatever k; null
- * question_words or pred: QMANN_EINVAL); then QMANN_EUNSUPPORTED for a Hamming model; then QMANN_EINVAL for k = 0,
+ * QMANN_ATT_FIXED models only: a Hamming V0 / V1 model returns QMANN_EUNSUPPORTED here and is served by
+ * qmann_model_ask_words_top_packed below (its softmax is per slot (V1) or over up to 2 049 bins (V0), a different selection).
+ * What qmann_model_ask_words refuses or answers without work is answered FIRST and as there (nothing memorised: QMANN_EINVAL;
+ * n_query = 0: QMANN_OK whatever k; null question_words or pred: QMANN_EINVAL); then QMANN_EUNSUPPORTED for a Hamming model; then QMANN_EINVAL for k = 0,
  * k > QMANN_MAX_TOP_SLOTS, a null top_slot or top_p.  A refused call launches nothing and leaves every output as it was. */
 int qmann_model_ask_words_top(qmann_model *m, const uint16_t *question_words, uint32_t max_q_words, uint32_t n_query,
                               const uint32_t *answer, uint32_t *pred, float *cost, uint32_t *match,
                               uint32_t k, uint32_t *top_slot, float *top_p, void *stream);
+
+/* qmann_model_ask_words_top for a Hamming V0 / V1 model: the same arguments and outputs, the rows those of
+ * qmann_hops_shared_top_packed (qmann_batch.h) on the packed memory the model holds.  It takes the path qmann_model_ask_words
+ * takes for such a model: the unsplit packed call, or with qmann_model_enable_split_asks_packed on and a memory beyond LDS the
+ * split call in chunks of floor(budget / share) questions, each chunk writing its block of rows at q0 . n_hop . k.  pred, cost,
+ * match, qmann_model_last_u and what qmann_model_last_topk ranks are those of qmann_model_ask_words; nothing is allocated once
+ * the question workspace has its size, so the call can be captured in a graph and replayed.
+ * What qmann_model_ask_words refuses or answers without work is answered FIRST and as there; then QMANN_EUNSUPPORTED for a
+ * QMANN_ATT_FIXED model (qmann_model_ask_words_top serves those); then QMANN_EINVAL for k = 0, k > QMANN_MAX_TOP_SLOTS, a null
+ * top_slot or top_p.  A refused call launches nothing and leaves every output as it was. */
+int qmann_model_ask_words_top_packed(qmann_model *m, const uint16_t *question_words, uint32_t max_q_words, uint32_t n_query,
+                                     const uint32_t *answer, uint32_t *pred, float *cost, uint32_t *match,
+                                     uint32_t k, uint32_t *top_slot, float *top_p, void *stream);
 
 /* Opt-in: asks through qmann_hops_shared_split_i8 (qmann_batch.h).  Without this call every call above behaves as described.
  * The model allocates `scratch_bytes` of workspace HERE (freed by qmann_model_destroy; never regrown inside an ask, so asks

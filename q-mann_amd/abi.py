@@ -177,6 +177,10 @@ _proto("qmann_hops_shared_split_top_i8", C.c_int, [C.POINTER(Net), _vp, _vp, C.c
                                                    C.c_uint32, C.c_uint32, _vp, C.c_size_t, _vp])
 _proto("qmann_hops_shared_packed", C.c_int, [C.POINTER(Net), _vp, C.c_size_t, _vp, C.c_size_t, C.c_uint32, _vp, _vp,
                                              C.POINTER(Taps), C.c_uint32, _vp])
+_proto("qmann_hops_shared_top_packed", C.c_int, [C.POINTER(Net), _vp, C.c_size_t, _vp, C.c_size_t, C.c_uint32, _vp, _vp,
+                                                 C.c_uint32, _vp, _vp, C.c_uint32, _vp])
+_proto("qmann_hops_shared_split_top_packed", C.c_int, [C.POINTER(Net), _vp, C.c_size_t, _vp, C.c_size_t, C.c_uint32, _vp, _vp,
+                                                       C.c_uint32, _vp, _vp, C.c_uint32, C.c_uint32, _vp, C.c_size_t, _vp])
 _proto("qmann_hops_shared_split_packed_ws_bytes", C.c_size_t, [C.POINTER(Net), C.c_uint32, C.c_uint32])
 _proto("qmann_hops_shared_split_packed_slices", C.c_uint32, [C.POINTER(Net), C.c_uint32, C.c_uint32])
 _proto("qmann_hops_shared_split_packed", C.c_int, [C.POINTER(Net), _vp, C.c_size_t, _vp, C.c_size_t, C.c_uint32, _vp, _vp,
@@ -225,6 +229,8 @@ _proto("qmann_model_forward_shared_words", C.c_int, [_vp, _vp, C.c_uint32, C.c_u
 _proto("qmann_model_memorize_words", C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _vp])
 _proto("qmann_model_ask_words", C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, _vp])
 _proto("qmann_model_ask_words_top", C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp])
+_proto("qmann_model_ask_words_top_packed", C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp,
+                                                     _vp])
 _proto("qmann_model_memory_rows", C.c_uint32, [_vp])
 _proto("qmann_model_forward_bow", C.c_int, [_vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, _vp])
 _proto("qmann_model_enable_split_asks", C.c_int, [_vp, C.c_size_t, _vp])

@@ -16,7 +16,7 @@
 // Unlike the fixed-point form the tile saves little vector work -- a packed row costs a handful of operations per query --;
 // what it shares is one read of the plane from L2 and that load's latency.
 // A last tile with fewer than QT queries scans with a live query's constants in the spare places and drops their sums.
-#include "hops_shared_ham.h"
+#include "hops_attended_ham.h"
 
 namespace {
 
@@ -26,9 +26,11 @@ constexpr size_t kSharedLdsLimit = 160 * 1024 - 1024;          // as qmann_hops_
 
 // LPRK: lanes per key row (16 LPRK bytes); DP: padded embedding width; MODE: kModeV0 / kModeV1; NB: planes; QT: queries per
 // workgroup.  per_q: bytes of LDS per query (ham_lds_bytes); a.max_slots = n_slots >= 1
-template <int LPRK, int DP, int MODE, int NB, int QT>
+// TOP (qmann_hops_shared_top_packed): every query's k most attended slots of the hop go to tp.slot / tp.p (hops_attended_ham.h).
+// The TOP builds are instantiations of their own: the others take an EMPTY last argument and keep their device code.
+template <int LPRK, int DP, int MODE, int NB, int QT, bool TOP = false>
 __global__ void __launch_bounds__(kBlock, 1)
-k_hops_shared_ham(const HopArgs a, const uint32_t n_query, const uint32_t per_q)
+k_hops_shared_ham(const HopArgs a, const uint32_t n_query, const uint32_t per_q, const HamTop<TOP> tp)
 {
     static_assert(mode_is_planes(MODE), "packed planes only");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -98,11 +100,18 @@ k_hops_shared_ham(const HopArgs a, const uint32_t n_query, const uint32_t per_q)
         for (uint32_t t = 0; t < nq; t++) {
             const HamQueryLds L = slice(t);
             const size_t tap_base = ((size_t)h * n_query + q0 + t) * S;
-            const uint32_t n_live = mode_is_v0(MODE)
-                ? ham_hist_softmax_survivors(a, h, S, nbins, tap_base, L.sc, L.v0_hist, L.v0_p, L.v0_kp, L.live_row, L.live_kp, L.misc, L.red, tid, lane, wave)
-                : ham_slot_softmax_survivors(a, h, S, scale, tap_base, L.sc, L.live_row, L.live_kp, L.misc, L.red, tid, lane, wave);
+            uint32_t n_live;
+            if constexpr (TOP && !mode_is_v0(MODE))                  // (V1: the selection runs inside, while the scores are there)
+                n_live = ham_slot_softmax_survivors(a, h, S, scale, tap_base, L.sc, L.live_row, L.live_kp, L.misc, L.red, tid, lane, wave,
+                                                    HamSelectV1{tp, (size_t)(q0 + t) * a.n_hop + h, S, L.sc, ham_att_words(L), tid, lane, wave});
+            else
+                n_live = mode_is_v0(MODE)
+                    ? ham_hist_softmax_survivors(a, h, S, nbins, tap_base, L.sc, L.v0_hist, L.v0_p, L.v0_kp, L.live_row, L.live_kp, L.misc, L.red, tid, lane, wave)
+                    : ham_slot_softmax_survivors(a, h, S, scale, tap_base, L.sc, L.live_row, L.live_kp, L.misc, L.red, tid, lane, wave);
             auto kp_of_row = [&](uint32_t r) { return mode_is_v0(MODE) ? (int)L.v0_kp[L.sc[r]] : (int)L.sc[r]; };
             finish_hop<DP>(a, q0 + t, h, 0u, S, n_live, L.live_row, L.live_kp, kp_of_row, L.ku, L.u_f, L.o_f, tid);
+            if constexpr (TOP && mode_is_v0(MODE))
+                ham_attended_select_v0(tp, (size_t)(q0 + t) * a.n_hop + h, S, nbins, L.sc, L.v0_hist, L.v0_p, ham_att_words(L), tid, lane, wave);
         }
     }
     for (uint32_t t = 0; t < nq; t++)
@@ -143,9 +152,10 @@ uint32_t qmann_hops_shared_packed_tile(const qmann_net *net, uint32_t n_slots, u
     return choose_qt_ham(per_q, n_query);
 }
 
-int qmann_hops_shared_packed(const qmann_net *net, const uint64_t *key_planes, size_t key_hop_stride, const int8_t *vals,
-                             size_t val_hop_stride, uint32_t n_slots, const float *u0, float *u_out, const qmann_taps *taps,
-                             uint32_t n_query, void *stream)
+// tp: null, or the outputs of qmann_hops_shared_top_packed -- the same launch in its TOP build
+static int hops_shared_packed_impl(const qmann_net *net, const uint64_t *key_planes, size_t key_hop_stride, const int8_t *vals,
+                                   size_t val_hop_stride, uint32_t n_slots, const float *u0, float *u_out, const qmann_taps *taps,
+                                   uint32_t n_query, void *stream, const HamTop<true> *tp)
 {
     QmBatched qm_scope;
     static const uint32_t no_row_off = 0;                     // this call has no row_off: the shared checks want a non-null one
@@ -164,6 +174,7 @@ int qmann_hops_shared_packed(const qmann_net *net, const uint64_t *key_planes, s
     if (Dp / 64 * nb * 8 < 16) return QMANN_EUNSUPPORTED;     // Dp = 64 with a single plane: a key row is half a 16-byte load
     if (n_query == 0) return QMANN_OK;
     if (qm_too_many_queries(n_query)) return QMANN_ERANGE;
+    if (tp && !ham_top_args_ok(tp->k, tp->slot, tp->p)) return QMANN_EINVAL;     // behind every refusal of the base call
 
     const bool v1 = net->attention_mode == QMANN_ATT_HAMMING_V1;
     const uint32_t qt = choose_qt_ham(per_q, n_query);
@@ -173,14 +184,36 @@ int qmann_hops_shared_packed(const qmann_net *net, const uint64_t *key_planes, s
             qm_dispatch<1, 2, 4, 8>(qt, [&](auto t) {
                 constexpr int DP = decltype(dp)::value, NB = decltype(n)::value, QT = decltype(t)::value, LPRK = (DP / 64) * NB * 8 / 16;
                 if constexpr (LPRK >= 1) {                      // (no instantiation for the case refused above)
-                    if (v1) qm_launch(k_hops_shared_ham<LPRK, DP, kModeV1, NB, QT>, qm_cdiv(n_query, qt), dim3(kBlock), (size_t)qt * per_q, st, a, n_query, (uint32_t)per_q);
-                    else qm_launch(k_hops_shared_ham<LPRK, DP, kModeV0, NB, QT>, qm_cdiv(n_query, qt), dim3(kBlock), (size_t)qt * per_q, st, a, n_query, (uint32_t)per_q);
+                    const dim3 grid(qm_cdiv(n_query, qt));
+                    const size_t lds = (size_t)qt * per_q;
+                    if (tp) {
+                        if (v1) qm_launch(k_hops_shared_ham<LPRK, DP, kModeV1, NB, QT, true>, grid, dim3(kBlock), lds, st, a, n_query, (uint32_t)per_q, *tp);
+                        else qm_launch(k_hops_shared_ham<LPRK, DP, kModeV0, NB, QT, true>, grid, dim3(kBlock), lds, st, a, n_query, (uint32_t)per_q, *tp);
+                    } else {
+                        if (v1) qm_launch(k_hops_shared_ham<LPRK, DP, kModeV1, NB, QT>, grid, dim3(kBlock), lds, st, a, n_query, (uint32_t)per_q, HamTop<false>{});
+                        else qm_launch(k_hops_shared_ham<LPRK, DP, kModeV0, NB, QT>, grid, dim3(kBlock), lds, st, a, n_query, (uint32_t)per_q, HamTop<false>{});
+                    }
                 }
             });
         });
     });
     QM_LAUNCH_CHECK();
     return qm_scope.rc();
+}
+
+int qmann_hops_shared_packed(const qmann_net *net, const uint64_t *key_planes, size_t key_hop_stride, const int8_t *vals,
+                             size_t val_hop_stride, uint32_t n_slots, const float *u0, float *u_out, const qmann_taps *taps,
+                             uint32_t n_query, void *stream)
+{
+    return hops_shared_packed_impl(net, key_planes, key_hop_stride, vals, val_hop_stride, n_slots, u0, u_out, taps, n_query, stream, nullptr);
+}
+
+int qmann_hops_shared_top_packed(const qmann_net *net, const uint64_t *key_planes, size_t key_hop_stride, const int8_t *vals,
+                                 size_t val_hop_stride, uint32_t n_slots, const float *u0, float *u_out, uint32_t k,
+                                 uint32_t *top_slot, float *top_p, uint32_t n_query, void *stream)
+{
+    const HamTop<true> tp{top_slot, top_p, k};
+    return hops_shared_packed_impl(net, key_planes, key_hop_stride, vals, val_hop_stride, n_slots, u0, u_out, nullptr, n_query, stream, &tp);
 }
 
 }  // extern "C"

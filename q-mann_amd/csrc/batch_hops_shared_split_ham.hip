@@ -25,7 +25,7 @@
 // The scores go to the workspace straight from the scan's retire step, two bytes per row and query.  The 2^x and exp_plan bases
 // keep their serial float total in slot order: block_serial_total_f32 then walks the scores in the workspace (global memory, L2
 // hits) instead of LDS -- right, but not fast at length.
-#include "hops_shared_ham.h"
+#include "hops_attended_ham.h"
 
 namespace {
 
@@ -189,10 +189,13 @@ k_shared_split_scan_ham(const HopArgs a, const uint32_t n_query, const uint32_t 
 
 // DP: padded embedding width; MODE: kModeV0 / kModeV1.  nbins: num_bit . D + 1; scale: the unit of a V1 score, 2^-num_bit.
 // Dynamic LDS: kOffScores bytes (HamQueryLds without the score array) plus, for V0, v0_table_bytes(nbins).
-template <int DP, int MODE>
+// TOP (qmann_hops_shared_split_top_packed): the query's k most attended slots of this hop go to tp.slot / tp.p
+// (hops_attended_ham.h, the scores read from the workspace); the other builds take an EMPTY last argument and keep their device
+// code.
+template <int DP, int MODE, bool TOP = false>
 __global__ void __launch_bounds__(kBlock)
 k_shared_split_finish_ham(const HopArgs a, const uint32_t n_query, const uint32_t h, const HamSplitWs w, const uint32_t nbins,
-                          const float scale)
+                          const float scale, const HamTop<TOP> tp)
 {
     static_assert(mode_is_planes(MODE), "packed planes only");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -218,11 +221,18 @@ k_shared_split_finish_ham(const HopArgs a, const uint32_t n_query, const uint32_
     __syncthreads();
 
     const size_t tap_base = ((size_t)h * n_query + q) * S;
-    const uint32_t n_live = mode_is_v0(MODE)
-        ? ham_hist_softmax_survivors(a, h, S, nbins, tap_base, sc, L.v0_hist, L.v0_p, L.v0_kp, L.live_row, L.live_kp, L.misc, L.red, tid, lane, wave)
-        : ham_slot_softmax_survivors(a, h, S, scale, tap_base, sc, L.live_row, L.live_kp, L.misc, L.red, tid, lane, wave);
+    uint32_t n_live;
+    if constexpr (TOP && !mode_is_v0(MODE))                          // (V1: the selection runs inside, while the scores are there)
+        n_live = ham_slot_softmax_survivors(a, h, S, scale, tap_base, sc, L.live_row, L.live_kp, L.misc, L.red, tid, lane, wave,
+                                            HamSelectV1{tp, (size_t)q * a.n_hop + h, S, sc, ham_att_words(L), tid, lane, wave});
+    else
+        n_live = mode_is_v0(MODE)
+            ? ham_hist_softmax_survivors(a, h, S, nbins, tap_base, sc, L.v0_hist, L.v0_p, L.v0_kp, L.live_row, L.live_kp, L.misc, L.red, tid, lane, wave)
+            : ham_slot_softmax_survivors(a, h, S, scale, tap_base, sc, L.live_row, L.live_kp, L.misc, L.red, tid, lane, wave);
     auto kp_of_row = [&](uint32_t r) { return mode_is_v0(MODE) ? (int)L.v0_kp[sc[r]] : (int)sc[r]; };
     finish_hop<DP>(a, q, h, 0u, S, n_live, L.live_row, L.live_kp, kp_of_row, L.ku, L.u_f, L.o_f, tid);
+    if constexpr (TOP && mode_is_v0(MODE))
+        ham_attended_select_v0(tp, (size_t)q * a.n_hop + h, S, nbins, sc, L.v0_hist, L.v0_p, ham_att_words(L), tid, lane, wave);
 
     if (h + 1 < a.n_hop) {
         if (tid < D) u_g[tid] = L.u_f[tid];
@@ -260,9 +270,11 @@ uint32_t qmann_hops_shared_split_packed_slices(const qmann_net *net, uint32_t n_
     return w.n_slices;
 }
 
-int qmann_hops_shared_split_packed(const qmann_net *net, const uint64_t *key_planes, size_t key_hop_stride, const int8_t *vals,
-                                   size_t val_hop_stride, uint32_t n_slots, const float *u0, float *u_out, const qmann_taps *taps,
-                                   uint32_t n_query, uint32_t n_slices, void *ws, size_t ws_bytes, void *stream)
+// tp: null, or the outputs of qmann_hops_shared_split_top_packed -- the same launches, the finish kernel in its TOP build
+static int hops_shared_split_packed_impl(const qmann_net *net, const uint64_t *key_planes, size_t key_hop_stride, const int8_t *vals,
+                                         size_t val_hop_stride, uint32_t n_slots, const float *u0, float *u_out,
+                                         const qmann_taps *taps, uint32_t n_query, uint32_t n_slices, void *ws, size_t ws_bytes,
+                                         void *stream, const HamTop<true> *tp)
 {
     QmBatched qm_scope;
     static const uint32_t no_row_off = 0;                     // this call has no row_off: the shared checks want a non-null one
@@ -282,6 +294,7 @@ int qmann_hops_shared_split_packed(const qmann_net *net, const uint64_t *key_pla
     if (n_query == 0) return QMANN_OK;
     if (qm_too_many_queries(n_query)) return QMANN_ERANGE;
     if (ws_bytes < (size_t)n_query * split_bytes_per_query(net, n_slots)) return QMANN_EINVAL;
+    if (tp && !ham_top_args_ok(tp->k, tp->slot, tp->p)) return QMANN_EINVAL;     // behind every refusal of the base call
 
     const bool v1 = net->attention_mode == QMANN_ATT_HAMMING_V1;
     const uint32_t nbins = nb * net->dim_emb + 1u;
@@ -312,12 +325,35 @@ int qmann_hops_shared_split_packed(const qmann_net *net, const uint64_t *key_pla
                     }
                 });
             });
-            if (v1) qm_launch(k_shared_split_finish_ham<DP, kModeV1>, n_query, dim3(kBlock), finish_lds, st, a, n_query, h, w, nbins, scale);
-            else qm_launch(k_shared_split_finish_ham<DP, kModeV0>, n_query, dim3(kBlock), finish_lds, st, a, n_query, h, w, nbins, scale);
+            if (tp) {
+                if (v1) qm_launch(k_shared_split_finish_ham<DP, kModeV1, true>, n_query, dim3(kBlock), finish_lds, st, a, n_query, h, w, nbins, scale, *tp);
+                else qm_launch(k_shared_split_finish_ham<DP, kModeV0, true>, n_query, dim3(kBlock), finish_lds, st, a, n_query, h, w, nbins, scale, *tp);
+            } else {
+                if (v1) qm_launch(k_shared_split_finish_ham<DP, kModeV1>, n_query, dim3(kBlock), finish_lds, st, a, n_query, h, w, nbins, scale, HamTop<false>{});
+                else qm_launch(k_shared_split_finish_ham<DP, kModeV0>, n_query, dim3(kBlock), finish_lds, st, a, n_query, h, w, nbins, scale, HamTop<false>{});
+            }
         });
     }
     QM_LAUNCH_CHECK();
     return qm_scope.rc();
+}
+
+int qmann_hops_shared_split_packed(const qmann_net *net, const uint64_t *key_planes, size_t key_hop_stride, const int8_t *vals,
+                                   size_t val_hop_stride, uint32_t n_slots, const float *u0, float *u_out, const qmann_taps *taps,
+                                   uint32_t n_query, uint32_t n_slices, void *ws, size_t ws_bytes, void *stream)
+{
+    return hops_shared_split_packed_impl(net, key_planes, key_hop_stride, vals, val_hop_stride, n_slots, u0, u_out, taps, n_query,
+                                         n_slices, ws, ws_bytes, stream, nullptr);
+}
+
+int qmann_hops_shared_split_top_packed(const qmann_net *net, const uint64_t *key_planes, size_t key_hop_stride, const int8_t *vals,
+                                       size_t val_hop_stride, uint32_t n_slots, const float *u0, float *u_out, uint32_t k,
+                                       uint32_t *top_slot, float *top_p, uint32_t n_query, uint32_t n_slices, void *ws,
+                                       size_t ws_bytes, void *stream)
+{
+    const HamTop<true> tp{top_slot, top_p, k};
+    return hops_shared_split_packed_impl(net, key_planes, key_hop_stride, vals, val_hop_stride, n_slots, u0, u_out, nullptr, n_query,
+                                         n_slices, ws, ws_bytes, stream, &tp);
 }
 
 }  // extern "C"

@@ -351,9 +351,16 @@ __device__ __forceinline__ uint32_t ham_hist_softmax_survivors(const HopArgs &a,
 
 // Every other mode: per slot (max, sum of exp in double, quotient) with the threshold / code_lo shortcut of k_hops_ham (its
 // comments hold the reasoning); `scale`: the unit of a score.  When the survivor list overflows, sc holds Q(p) per row afterwards.
+// `select` (hops_attended_ham.h; by default nothing): called by the whole workgroup behind the survivor search, while the scores
+// are still in sc, with p_of(score) -- the probability of a slot with that int16 score, by the expression the tap path writes.
+struct HamNoSelect {
+    template <typename POf> __device__ __forceinline__ void operator()(POf) const {}
+};
+template <typename Select = HamNoSelect>
 __device__ __forceinline__ uint32_t ham_slot_softmax_survivors(const HopArgs &a, uint32_t h, uint32_t S, float scale, size_t tap_base,
                                                                int16_t *sc, uint32_t *live_row, uint8_t *live_kp, uint32_t *misc,
-                                                               double *red, uint32_t tid, uint32_t lane, uint32_t wave)
+                                                               double *red, uint32_t tid, uint32_t lane, uint32_t wave,
+                                                               const Select select = Select{})
 {
     const QFmt fa = a.act[h];
     const SmCfg smc = sm_cfg(a, h);
@@ -387,6 +394,7 @@ __device__ __forceinline__ uint32_t ham_slot_softmax_survivors(const HopArgs &a,
     }
     __syncthreads();
     const uint32_t n_live = misc[0];
+    select([&](int score) { return sm_quot(sm_exp(sm_scaled((float)score * scale, smc) - xmax, smc), total, smc); });
     if (n_live > (uint32_t)kLiveCap) {                  // keep the overflow path exact: park Q(p) in sc
         for (uint32_t r = tid; r < S; r += kBlock) {
             const float p = sm_quot(sm_exp(slot_x(r) - xmax, smc), total, smc);

@@ -622,9 +622,11 @@ int qmann_model_memorize_words(qmann_model *m, const uint16_t *story_words, uint
     return QMANN_OK;
 }
 
-// qmann_model_ask_words (top = false) and qmann_model_ask_words_top (top = true: k, top_slot, top_p as that call takes them)
+// qmann_model_ask_words (kAskPlain), qmann_model_ask_words_top (kAskTop: fixed-point models) and
+// qmann_model_ask_words_top_packed (kAskTopPacked: Hamming V0 / V1 models); k, top_slot, top_p as the top calls take them
+enum AskTop { kAskPlain, kAskTop, kAskTopPacked };
 static int ask_words_impl(qmann_model *m, const uint16_t *question_words, uint32_t max_q_words, uint32_t n_query,
-                          const uint32_t *answer, uint32_t *pred, float *cost, uint32_t *match, bool top, uint32_t k,
+                          const uint32_t *answer, uint32_t *pred, float *cost, uint32_t *match, AskTop top, uint32_t k,
                           uint32_t *top_slot, float *top_p, void *stream)
 {
     QmBatched qm_scope;
@@ -634,7 +636,7 @@ static int ask_words_impl(qmann_model *m, const uint16_t *question_words, uint32
     m->last_n_query = 0;                                // (set again where this call succeeds)
     if (!question_words || !pred) return QMANN_EINVAL;
     if (top) {                                          // behind the base call's refusals, and here: an ask must not fail behind its embedding
-        if (packed_mode(m->net)) return QMANN_EUNSUPPORTED;
+        if (packed_mode(m->net) != (top == kAskTopPacked)) return QMANN_EUNSUPPORTED;     // each form serves its own models
         if (k == 0 || k > QMANN_MAX_TOP_SLOTS || !top_slot || !top_p) return QMANN_EINVAL;
     }
     DeviceScope on(m->device);
@@ -655,14 +657,20 @@ static int ask_words_impl(qmann_model *m, const uint16_t *question_words, uint32
             const float *u0 = m->u0 + (size_t)q0 * m->D;
             float *u = m->u + (size_t)q0 * m->D;
             const size_t row0 = (size_t)q0 * m->H * k;     // (top: the chunk's own block of rows)
-            rc = packed ? qmann_hops_shared_split_packed(&m->net, m->mem_planes, key_plane, m->mem_vals, plane, S, u0, u, nullptr, nq, 0,
+            rc = packed && top ? qmann_hops_shared_split_top_packed(&m->net, m->mem_planes, key_plane, m->mem_vals, plane, S, u0, u, k,
+                                                                    top_slot + row0, top_p + row0, nq, 0, m->split_ws,
+                                                                    m->split_bytes, stream)
+                 : packed ? qmann_hops_shared_split_packed(&m->net, m->mem_planes, key_plane, m->mem_vals, plane, S, u0, u, nullptr, nq, 0,
                                                          m->split_ws, m->split_bytes, stream)
                  : top  ? qmann_hops_shared_split_top_i8(&m->net, m->mem_keys, m->mem_vals, plane, S, u0, u, k, top_slot + row0,
                                                          top_p + row0, nq, 0, m->split_ws, m->split_bytes, stream)
                         : qmann_hops_shared_split_i8(&m->net, m->mem_keys, m->mem_vals, plane, S, u0, u, nullptr, nq, 0, m->split_ws,
                                                      m->split_bytes, stream);
         }
-    } else if (packed)
+    } else if (packed && top)
+        rc = qmann_hops_shared_top_packed(&m->net, m->mem_planes, key_plane, m->mem_vals, plane, S, m->u0, m->u, k, top_slot, top_p,
+                                          n_query, stream);
+    else if (packed)
         rc = qmann_hops_shared_packed(&m->net, m->mem_planes, key_plane, m->mem_vals, plane, S, m->u0, m->u, nullptr, n_query, stream);
     else if (top)
         rc = qmann_hops_shared_top_i8(&m->net, m->mem_keys, m->mem_vals, plane, S, m->u0, m->u, k, top_slot, top_p, n_query, stream);
@@ -678,14 +686,21 @@ static int ask_words_impl(qmann_model *m, const uint16_t *question_words, uint32
 int qmann_model_ask_words(qmann_model *m, const uint16_t *question_words, uint32_t max_q_words, uint32_t n_query,
                           const uint32_t *answer, uint32_t *pred, float *cost, uint32_t *match, void *stream)
 {
-    return ask_words_impl(m, question_words, max_q_words, n_query, answer, pred, cost, match, false, 0, nullptr, nullptr, stream);
+    return ask_words_impl(m, question_words, max_q_words, n_query, answer, pred, cost, match, kAskPlain, 0, nullptr, nullptr, stream);
 }
 
 int qmann_model_ask_words_top(qmann_model *m, const uint16_t *question_words, uint32_t max_q_words, uint32_t n_query,
                               const uint32_t *answer, uint32_t *pred, float *cost, uint32_t *match, uint32_t k,
                               uint32_t *top_slot, float *top_p, void *stream)
 {
-    return ask_words_impl(m, question_words, max_q_words, n_query, answer, pred, cost, match, true, k, top_slot, top_p, stream);
+    return ask_words_impl(m, question_words, max_q_words, n_query, answer, pred, cost, match, kAskTop, k, top_slot, top_p, stream);
+}
+
+int qmann_model_ask_words_top_packed(qmann_model *m, const uint16_t *question_words, uint32_t max_q_words, uint32_t n_query,
+                                     const uint32_t *answer, uint32_t *pred, float *cost, uint32_t *match, uint32_t k,
+                                     uint32_t *top_slot, float *top_p, void *stream)
+{
+    return ask_words_impl(m, question_words, max_q_words, n_query, answer, pred, cost, match, kAskTopPacked, k, top_slot, top_p, stream);
 }
 
 uint32_t qmann_model_memory_rows(const qmann_model *m) { return m ? m->mem_rows : 0u; }

@@ -443,6 +443,47 @@ class QNet:
         self._split_ws = ws                                                       # alive until the next call: the launch is asynchronous
         return (u_out, tobj) if taps else u_out
 
+    def hops_shared_top_packed(self, key_planes, vals, n_slots, u0, k):
+        """qmann_hops_shared_top_packed: hops_shared_packed plus, per query and hop, the k most attended slots and their
+        probabilities: (u_out, top_slot int32 [B][H][k], top_p float32 [B][H][k]), larger probability first, equal
+        probabilities: lower slot first; entries past n_slots are slot -1 (0xFFFFFFFF), p 0.  Arguments as hops_shared_packed."""
+        B = u0.shape[0]
+        nb = key_planes.shape[-1]
+        assert vals.shape in ((self.H, n_slots, self.Dp), (1, n_slots, self.Dp))
+        assert key_planes.shape == (vals.shape[0], n_slots, self.Dp // 64, nb)
+        assert key_planes.is_contiguous() and vals.is_contiguous()
+        u_out = torch.empty_like(u0)
+        top_slot, top_p = _top_out(self.dev, B, self.H, k)
+        per_hop = vals.shape[0] == self.H
+        key_stride = n_slots * (self.Dp // 64) * nb * 8 if per_hop else 0         # one plane for several hops: tied
+        val_stride = n_slots * self.Dp if per_hop else 0
+        abi.check(abi.lib.qmann_hops_shared_top_packed(C.byref(self.net), _ptr(key_planes), key_stride, _ptr(vals), val_stride,
+                                                       n_slots, _ptr(u0), _ptr(u_out), k, _ptr(top_slot), _ptr(top_p), B,
+                                                       self._s()), "qmann_hops_shared_top_packed")
+        return u_out, top_slot, top_p
+
+    def hops_shared_split_top_packed(self, key_planes, vals, n_slots, u0, k, n_slices=0):
+        """qmann_hops_shared_split_top_packed: hops_shared_top_packed with the slots cut into n_slices slices (0: the library's
+        choice); the workspace is allocated here, of the size hops_shared_split_packed takes.  Results as hops_shared_top_packed."""
+        B = u0.shape[0]
+        nb = key_planes.shape[-1]
+        assert vals.shape in ((self.H, n_slots, self.Dp), (1, n_slots, self.Dp))
+        assert key_planes.shape == (vals.shape[0], n_slots, self.Dp // 64, nb)
+        assert key_planes.is_contiguous() and vals.is_contiguous()
+        u_out = torch.empty_like(u0)
+        top_slot, top_p = _top_out(self.dev, B, self.H, k)
+        nbytes = int(abi.lib.qmann_hops_shared_split_packed_ws_bytes(C.byref(self.net), n_slots, B))
+        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=self.dev)       # (torch allocations are 16-byte aligned)
+        per_hop = vals.shape[0] == self.H
+        key_stride = n_slots * (self.Dp // 64) * nb * 8 if per_hop else 0
+        val_stride = n_slots * self.Dp if per_hop else 0
+        abi.check(abi.lib.qmann_hops_shared_split_top_packed(C.byref(self.net), _ptr(key_planes), key_stride, _ptr(vals),
+                                                             val_stride, n_slots, _ptr(u0), _ptr(u_out), k, _ptr(top_slot),
+                                                             _ptr(top_p), B, n_slices, _ptr(ws), nbytes, self._s()),
+                  "qmann_hops_shared_split_top_packed")
+        self._split_ws = ws                                                       # alive until the next call: the launch is asynchronous
+        return u_out, top_slot, top_p
+
     def answer(self, u, answer=None, want_probs=False, serial=False):
         """serial=True: qmann_answer_f32_serial (the reference's order of additions, bit-equal logits); default: the library's
         choice (the fused bf16 form at the bAbI shapes, within 1e-5 on the probabilities)"""
@@ -622,6 +663,17 @@ class HostModel:
         abi.check(abi.lib.qmann_model_ask_words_top(self.h, _ptr(question_words), question_words.shape[1], B, _ptr(answer),
                                                     _ptr(pred), _ptr(cost), _ptr(match), k, _ptr(top_slot), _ptr(top_p),
                                                     self._s()), "qmann_model_ask_words_top")
+        return pred, cost, match, top_slot, top_p
+
+    def ask_words_top_packed(self, question_words, k, answer=None):
+        """qmann_model_ask_words_top_packed: ask_words_top for a Hamming V0 / V1 model -- (pred, cost, match, top_slot int32
+        [B][H][k], top_p float32 [B][H][k]), rows of the memorised story as QNet.hops_shared_top_packed gives them"""
+        B = question_words.shape[0]
+        pred, cost, match = self._out(B, answer)
+        top_slot, top_p = _top_out(self.dev, B, self.cfg["n_hop"], k)
+        abi.check(abi.lib.qmann_model_ask_words_top_packed(self.h, _ptr(question_words), question_words.shape[1], B, _ptr(answer),
+                                                           _ptr(pred), _ptr(cost), _ptr(match), k, _ptr(top_slot), _ptr(top_p),
+                                                           self._s()), "qmann_model_ask_words_top_packed")
         return pred, cost, match, top_slot, top_p
 
     def forward_bow(self, story, question, row_off, max_slots, answer=None):
