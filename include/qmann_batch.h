@@ -395,6 +395,10 @@ int qmann_embed_story_idx(const qmann_net *net, const uint16_t *words, uint32_t 
                           int8_t *vals, size_t hop_stride, void *stream);
 int qmann_embed_query_idx(const qmann_net *net, const uint16_t *words, uint32_t max_words, const int8_t *t_q,
                           float *u0, uint32_t n_query, void *stream);
+/* the kernel form qmann_embed_story_idx would take for this call (QMANN_EMBED_VALU / _PER_HOP included), or the negative
+ * code the call would return -- for tests and timing tools that must know which kernel ran */
+enum { QMANN_EMBED_GATHER_LDS = 0, QMANN_EMBED_GATHER_L2 = 1, QMANN_EMBED_MFMA_PER_HOP = 2, QMANN_EMBED_MFMA_ALL_HOPS = 3 };
+int qmann_embed_story_idx_form(const qmann_net *net, const uint16_t *words, uint32_t max_words);
 
 /* Validation helper: *n_over (a device word, accumulated into) += the number of queries whose story is longer than
  * max_slots, i.e. would be cut by the hop kernels. */
@@ -416,7 +420,7 @@ size_t qmann_hops_shared_packed_lds_bytes(const qmann_net *net, uint32_t n_slots
 uint32_t qmann_hops_shared_packed_tile(const qmann_net *net, uint32_t n_slots, uint32_t n_query);
 
 /* The library's A/B switches (environment variables QMANN_NO_LEAN, QMANN_NO_MID, QMANN_NO_W7, QMANN_NO_TIED, QMANN_NO_TIGHT,
- * QMANN_SHARED_QT, QMANN_LEAN_SPARSE, QMANN_EMBED_VALU, QMANN_EMBED_GENERAL_EPILOGUE, QMANN_ANSWER_TWO_PASS: INTEGRATION.md) are read ONCE,
+ * QMANN_SHARED_QT, QMANN_LEAN_SPARSE, QMANN_EMBED_VALU, QMANN_EMBED_PER_HOP, QMANN_EMBED_GENERAL_EPILOGUE, QMANN_ANSWER_TWO_PASS: INTEGRATION.md) are read ONCE,
  * at the first call that needs one; no launch touches the environment afterwards.  A host that changes one later calls
  * this to have them read again -- from one thread, while no other thread is inside the library. */
 void qmann_tuning_reload(void);

@@ -197,6 +197,8 @@ _proto("qmann_quantize_table_i8", C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.
 _proto("qmann_embed_story_idx", C.c_int, [C.POINTER(Net), _vp, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(_vp),
                                           C.POINTER(_vp), _vp, _vp, C.c_size_t, _vp])
 _proto("qmann_embed_query_idx", C.c_int, [C.POINTER(Net), _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp])
+EMBED_GATHER_LDS, EMBED_GATHER_L2, EMBED_MFMA_PER_HOP, EMBED_MFMA_ALL_HOPS = 0, 1, 2, 3
+_proto("qmann_embed_story_idx_form", C.c_int, [C.POINTER(Net), _vp, C.c_uint32])
 _proto("qmann_embed_query", C.c_int, [C.POINTER(Net), _vp, _vp, _vp, C.c_uint32, _vp])
 _proto("qmann_bow_to_words", C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp])
 _proto("qmann_embed_story_rows", C.c_int, [C.POINTER(Net), _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp])

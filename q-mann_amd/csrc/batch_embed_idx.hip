@@ -885,6 +885,39 @@ static void fill_qkinds(EmbedIdxArgs &a)
     if (qm_tuning().embed_general_epilogue) a.qkinds = 0xFFFFFFFFu;     // A/B: ew_to_bytes everywhere
 }
 
+// ---- which kernel form a story-embedding call takes: the ONE decision (the launcher switches over it, qmann_embed_story_idx_form
+// reports it).  No HIP call, no state but qm_tuning(). --------------------------------------------------------------------------
+static inline uint32_t em_dict_k(uint32_t V) { return V <= 64u ? 64u : (V <= 128u ? 128u : 256u); }   // dictionary padded to the MFMA's K step
+// LDS of the gather-sum kernel: all 2 . n_hop tables as int16 [V + 1][Dp]; the per-wavefront word scratch
+static inline size_t ew_tab_lds(const qmann_net *net) { return (size_t)net->n_hop * 2 * (net->dim_input + 1u) * net->dim_emb_pad * 2u; }
+static inline size_t ew_wave_lds() { return (size_t)kWaves * kEwWaveBytes; }
+
+static int embed_story_form(const qmann_net *net, const uint16_t *words, uint32_t max_words)
+{
+    if (!net) return QMANN_EINVAL;
+    if (net->n_hop == 0 || net->n_hop > QMANN_MAX_HOP || net->dim_emb > net->dim_emb_pad) return QMANN_EINVAL;
+    if (max_words == 0 || max_words > (uint32_t)kMaxWords) return QMANN_ERANGE;
+    for (uint32_t h = 0; h < net->n_hop; h++)
+        if (!qm_fmt8(net->act[h]) || !qm_fmt8(net->w[h]) || !qm_fmt8(net->att[h])) return QMANN_ERANGE;
+    if (net->dim_emb_pad & 3u) return QMANN_EINVAL;
+    if (net->dim_emb_pad % 64 != 0) return QMANN_EUNSUPPORTED;          // 16 lanes x 4 columns per round
+    // dictionaries of up to 256 entries with 1.0 representable in every weight format: the matrix-core kernels
+    bool mfma_ok = net->dim_input <= 256 && net->dim_emb_pad == 64 && (max_words & 3u) == 0u && ((uintptr_t)words & 7u) == 0u &&
+                   !qm_tuning().embed_valu;
+    for (uint32_t h = 0; h < net->n_hop; h++) mfma_ok = mfma_ok && net->w[h].iwl >= 1;
+    if (mfma_ok) {
+        // joint-task dictionaries, several hops: every hop of a tile in one workgroup; QMANN_EMBED_PER_HOP keeps a workgroup per hop (A/B)
+        // (64-entry dictionaries -- task 1 -- gain nothing from it: 444 against 443 M q/s in an interleaved A/B with the K = 64
+        // instantiation at six wavefronts per SIMD; they keep a workgroup per hop)
+        if (em_dict_k(net->dim_input) == 256u && net->n_hop >= 2u && net->n_hop <= 3u && !qm_tuning().embed_per_hop) return QMANN_EMBED_MFMA_ALL_HOPS;
+        return QMANN_EMBED_MFMA_PER_HOP;
+    }
+    // small dictionaries: all tables in LDS as int16; larger ones are gathered from L2 (for dictionaries whose tables
+    // exceed LDS both alternatives to L2 gathers were measured on the 20-task joint set in round 1 and were slower:
+    // staging one hop's tables at a time, and one copy per CU shared by a 1024-thread workgroup)
+    return ew_tab_lds(net) + ew_wave_lds() <= 64 * 1024 ? QMANN_EMBED_GATHER_LDS : QMANN_EMBED_GATHER_L2;
+}
+
 }  // namespace
 
 extern "C" {
@@ -952,26 +985,22 @@ int qmann_embed_story_idx(const qmann_net *net, const uint16_t *words, uint32_t 
     fill_qkinds(a);
     if (rows_total == 0) return QMANN_OK;
     if ((net->dim_emb_pad & 3u) || (hop_stride & 3u) || ((uintptr_t)keys & 3u) || ((uintptr_t)vals & 3u)) return QMANN_EINVAL;
-    if (net->dim_emb_pad % 64 != 0) return QMANN_EUNSUPPORTED;          // 16 lanes x 4 columns per round
-    // dictionaries of up to 256 entries with 1.0 representable in every weight format: the matrix-core kernel
-    bool mfma_ok = net->dim_input <= 256 && net->dim_emb_pad == 64 && (max_words & 3u) == 0u && ((uintptr_t)words & 7u) == 0u &&
-                   !qm_tuning().embed_valu;
-    for (uint32_t h = 0; h < net->n_hop; h++) mfma_ok = mfma_ok && net->w[h].iwl >= 1;
-    if (mfma_ok) {
-        const uint32_t K = net->dim_input <= 64 ? 64u : (net->dim_input <= 128 ? 128u : 256u), Dp = net->dim_emb_pad;
-        hipStream_t st = (hipStream_t)stream;
+    const int form = embed_story_form(net, words, max_words);           // (what is left to refuse: a width that is no multiple of 64)
+    if (form < 0) return form;
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t Dp = net->dim_emb_pad;
+    switch (form) {
+    case QMANN_EMBED_MFMA_ALL_HOPS: {
+        // every hop of a tile in one workgroup, X built once per tile in chunks (k_embed_story_mfma_hops)
+        constexpr uint32_t nwh = 16u, K = 256u;
         const size_t tiles = ((size_t)rows_total + kEmRows - 1) / kEmRows;
-        // joint-task dictionaries, several hops: every hop of a tile in one workgroup, X built once per tile in chunks
-        // (k_embed_story_mfma_hops); QMANN_EMBED_PER_HOP keeps a workgroup per hop (A/B)
-        // (64-entry dictionaries -- task 1 -- gain nothing from it: 444 against 443 M q/s in an interleaved A/B with the K = 64
-        // instantiation at six wavefronts per SIMD; they keep a workgroup per hop)
-        if (K == 256u && net->n_hop >= 2u && net->n_hop <= 3u && !qm_tuning().embed_per_hop) {
-            constexpr uint32_t nwh = 16u;
-            const size_t lds = (size_t)net->n_hop * 2u * Dp * K + (size_t)nwh * (2u * kEmRows * 64u + kEmDupCap * 4u + 16u + kEmRows * 32u);
-            qm_launch_persistent(k_embed_story_mfma_hops<16, 4, 4>, (uint32_t)((tiles + nwh - 1) / nwh), QmPersistent{nwh, 4u}, lds, st, a);
-            QM_LAUNCH_CHECK();
-            return qm_scope.rc();
-        }
+        const size_t lds = (size_t)net->n_hop * 2u * Dp * K + (size_t)nwh * (2u * kEmRows * 64u + kEmDupCap * 4u + 16u + kEmRows * 32u);
+        qm_launch_persistent(k_embed_story_mfma_hops<16, 4, 4>, (uint32_t)((tiles + nwh - 1) / nwh), QmPersistent{nwh, 4u}, lds, st, a);
+        break;
+    }
+    case QMANN_EMBED_MFMA_PER_HOP: {
+        const uint32_t K = em_dict_k(net->dim_input);
+        const size_t tiles = ((size_t)rows_total + kEmRows - 1) / kEmRows;
         // T^T (2 x 64 x K bytes) is per workgroup: large dictionaries share it among 16 wavefronts
         const uint32_t nwv = K == 64 ? 8u : 16u;
         const size_t lds = 2u * (size_t)Dp * K + (size_t)nwv * (kEmRows * K + kEmRows * (Dp + 16u) + kEmDupCap * 4u + 16u);
@@ -982,21 +1011,28 @@ int qmann_embed_story_idx(const qmann_net *net, const uint16_t *words, uint32_t 
             qm_launch_persistent(k_embed_story_mfma<KS, NW>, (uint32_t)((tiles + nwv - 1) / nwv),
                                  QmPersistent{NW, (unsigned)em_waves_per_simd(KS), 0, net->n_hop}, lds, st, a);
         });
-        QM_LAUNCH_CHECK();
-        return qm_scope.rc();
+        break;
     }
-    const uint32_t need = (rows_total + kWaves * 4 - 1) / (kWaves * 4);
-    // small dictionaries: all tables in LDS as int16; larger ones are gathered from L2 (for dictionaries whose tables
-    // exceed LDS both alternatives to L2 gathers were measured on the 20-task joint set in round 1 and were slower:
-    // staging one hop's tables at a time, and one copy per CU shared by a 1024-thread workgroup)
-    const size_t tab_lds = (size_t)net->n_hop * 2 * (net->dim_input + 1u) * net->dim_emb_pad * 2u;
-    const size_t wave_lds = (size_t)kWaves * kEwWaveBytes;
-    if (tab_lds + wave_lds <= 64 * 1024)                                  // (118 registers: four wavefronts per SIMD)
-        qm_launch_persistent(k_embed_story_idx<true>, need, QmPersistent{kWaves, 4}, tab_lds + wave_lds, (hipStream_t)stream, a);
-    else
-        qm_launch_persistent(k_embed_story_idx<false>, need, QmPersistent{kWaves, 4}, wave_lds, (hipStream_t)stream, a);
+    case QMANN_EMBED_GATHER_LDS: {                                        // (118 registers: four wavefronts per SIMD)
+        const uint32_t need = (rows_total + kWaves * 4 - 1) / (kWaves * 4);
+        qm_launch_persistent(k_embed_story_idx<true>, need, QmPersistent{kWaves, 4}, ew_tab_lds(net) + ew_wave_lds(), st, a);
+        break;
+    }
+    case QMANN_EMBED_GATHER_L2: {
+        const uint32_t need = (rows_total + kWaves * 4 - 1) / (kWaves * 4);
+        qm_launch_persistent(k_embed_story_idx<false>, need, QmPersistent{kWaves, 4}, ew_wave_lds(), st, a);
+        break;
+    }
+    default:
+        return QMANN_EINVAL;
+    }
     QM_LAUNCH_CHECK();
     return qm_scope.rc();
+}
+
+int qmann_embed_story_idx_form(const qmann_net *net, const uint16_t *words, uint32_t max_words)
+{
+    return embed_story_form(net, words, max_words);
 }
 
 int qmann_embed_query_idx(const qmann_net *net, const uint16_t *words, uint32_t max_words, const int8_t *t_q, float *u0,
