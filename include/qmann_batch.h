@@ -346,7 +346,16 @@ int qmann_answer_topk_f32(const qmann_net *net, const float *w_ans, const float 
  *       tolerance (normaliser accumulated against the running maximum, hardware exp as the reference's __expf).
  *   probs != NULL: two kernels -- logits to the workspace, then the float path's softmax on them: probabilities bit-identical
  *       to qmann_answer_f32_serial on the same grid values.
- * logits_ws: caller-provided workspace, float [n_query][V] (the one-pass form keeps its per-slice records there). */
+ * logits_ws: caller-provided workspace, float [n_query][V], 8-byte aligned: the one-pass form keeps its per-slice records there
+ * (16 bytes each, holding a double), one per dictionary slice and query, at most ceil(V / 64) slices.  A dictionary of 1, 2 or 3
+ * answers has less workspace per query than one record: such a call takes the two-kernel form whatever `probs` is (the logits
+ * round trip costs nothing there), and its results are that form's, bit-identical to qmann_answer_f32_serial.  So do the exp_plan
+ * softmax base (no true exponential to rescale a running maximum by) and every call under QMANN_ANSWER_TWO_PASS (environment).
+ * Nothing is launched, no output is touched and the code returned is: QMANN_EINVAL for a null net, w_ans_i8, u, logits_ws or pred,
+ * dim_emb = 0, dim_input = 0, dim_emb_pad not a multiple of 64, dim_emb > dim_emb_pad; QMANN_ERANGE for an activation format (the
+ * last hop's) or a w_fmt that is no byte format (1 <= iwl + frac <= 7), a query's LDS beyond 128 KiB (dim_emb rounded up to 4,
+ * plus dim_input, floats), 2^24 queries or more; QMANN_OK for n_query = 0; QMANN_EUNSUPPORTED for a dim_emb_pad other than 64, 128
+ * or 256.  The checks run in this order; the first that fails decides. */
 int qmann_answer_i8(const qmann_net *net, const int8_t *w_ans_i8, qmann_fmt w_fmt, const float *u,
                     float *logits_ws, const uint32_t *answer, uint32_t *pred, float *probs, float *cost,
                     uint32_t *match, uint32_t n_query, void *stream);

@@ -22,11 +22,17 @@ namespace {
 template <bool TOPK> struct AnsTopK {};
 template <> struct AnsTopK<true> { uint32_t *idx; float *p; uint32_t k; };
 
+// small_lpq / small_vpt (PRECOMPUTED only; 0: not used): the shape of the k_answer_small build that serves this dictionary in the
+// float layer (lanes per query, adjacent logits per lane).  The double normaliser is then added up in THAT kernel's order -- a
+// lane's logits one after the other, the lanes pairwise as its butterfly joins them -- instead of this kernel's strided one: two
+// orders give totals one unit in the last place apart (2 and 2 + 2^-51 where two tied answers carry the sum), and the quotient
+// of a denormal e by them rounds to different floats (e / 2 of an odd denormal is a rounding midpoint).  With the same tree the
+// probabilities of qmann_answer_i8's two-kernel form are qmann_answer_f32_serial's bit for bit at every magnitude.
 template <bool PRECOMPUTED, bool TOPK = false>
 __global__ void __launch_bounds__(kBlock)
 k_answer(const float *__restrict__ w_ans, const float *__restrict__ u, const uint32_t *__restrict__ answer,
          uint32_t *__restrict__ pred, float *__restrict__ probs, float *cost, uint32_t *match, uint32_t D,
-         uint32_t V, uint32_t softmax_base, uint32_t n_query, const AnsTopK<TOPK> tk)
+         uint32_t V, uint32_t softmax_base, uint32_t n_query, uint32_t small_lpq, uint32_t small_vpt, const AnsTopK<TOPK> tk)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float *us = (float *)smem;            // [D]
@@ -80,7 +86,22 @@ k_answer(const float *__restrict__ w_ans, const float *__restrict__ u, const uin
     for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o);
     if (lane == 0) red_d[wave] = part;
     __syncthreads();
-    const double total = (red_d[0] + red_d[1]) + (red_d[2] + red_d[3]);
+    double total = (red_d[0] + red_d[1]) + (red_d[2] + red_d[3]);
+    if (PRECOMPUTED && small_lpq) {                  // (uniform) every wavefront forms k_answer_small's tree from the terms in LDS
+        const uint32_t sub = lane % small_lpq;       // 16 lanes per query there: the four rows of this wavefront do the same work
+        double t = 0.0;
+        for (uint32_t k = 0; k < small_vpt; k++) {
+            const uint32_t v = sub * small_vpt + k;
+            t += v < V ? (double)lg[v] : 0.0;        // (a lane's logits past V are zero terms there too)
+        }
+        t += __shfl(t, (int)(lane ^ 1u));                                // quad_perm [1,0,3,2]
+        t += __shfl(t, (int)(lane ^ 2u));                                // quad_perm [2,3,0,1]
+        t += __shfl(t, (int)((lane & ~7u) | (7u - (lane & 7u))));        // row_half_mirror
+        t += __shfl(t, (int)((lane & ~15u) | (15u - (lane & 15u))));     // row_mirror
+        for (uint32_t o = 16; o < small_lpq; o <<= 1) t += __shfl_xor(t, (int)o);
+        total = t;                                   // (every lane holds it)
+        __syncthreads();                             // all wavefronts have read the terms before the quotients replace them
+    }
 
     float bv = -INFINITY;
     uint32_t bi = 0;
@@ -819,6 +840,25 @@ k_answer_i8_combine(const AnsPart *__restrict__ part, const float *__restrict__ 
 
 }  // namespace
 
+// the k_answer_small build of a shape, and whether the float layer takes it (otherwise: k_answer, one workgroup per query)
+struct AnsSmallPlan {
+    uint32_t lpq, vpt, qpw;     // lanes per query, logits per lane (the 64-lane build is <64, 4, 4> whatever vpt says), queries per wavefront
+    size_t lds;
+    bool fits;
+};
+static AnsSmallPlan ans_small_plan(uint32_t D, uint32_t V)
+{
+    AnsSmallPlan p;
+    p.lpq = V <= 128 ? 16u : 64u;
+    const uint32_t qb = V <= 96 ? 2u : (V <= 128 ? 1u : 4u);
+    const uint32_t vpt = (V + p.lpq - 1) / p.lpq;
+    p.vpt = vpt <= 2 ? 2u : vpt <= 4 ? 4u : vpt <= 6 ? 6u : 8u;
+    p.qpw = kWave / p.lpq * qb;
+    p.lds = ((size_t)D * p.lpq * p.vpt + (size_t)kAnsWaves * p.qpw * D) * sizeof(float);
+    p.fits = V <= 256u && p.lds <= 78 * 1024;
+    return p;
+}
+
 extern "C" {
 
 // tk: null, or the outputs of qmann_answer_topk_f32 -- the serial-order kernel of the shape in its top-k build (the bookkeeping
@@ -855,12 +895,10 @@ static int answer_f32_impl(const qmann_net *net, const float *w_ans, const float
     // lane groups side by side in a wavefront (the reductions are most of the work there); the joint-task sizes: the whole
     // wavefront on four queries at once, every weight read from LDS used four times (that kernel is bound by LDS reads)
     // (two queries per lane group up to 96 logits: -6 % on this kernel at V = 80; with 8 logits per lane the second query's state spills)
-    const uint32_t lpq = V <= 128 ? 16u : 64u, qb = V <= 96 ? 2u : (V <= 128 ? 1u : 4u);
-    uint32_t vpt = (V + lpq - 1) / lpq;
-    vpt = vpt <= 2 ? 2u : vpt <= 4 ? 4u : vpt <= 6 ? 6u : 8u;
-    const uint32_t qpw = kWave / lpq * qb;
-    const size_t lds_small = ((size_t)D * lpq * vpt + (size_t)kAnsWaves * qpw * D) * sizeof(float);
-    if (V <= 256u && lds_small <= 78 * 1024) {              // W^T fits LDS twice per CU
+    const AnsSmallPlan sp = ans_small_plan(D, V);
+    const uint32_t lpq = sp.lpq, vpt = sp.vpt, qpw = sp.qpw;
+    const size_t lds_small = sp.lds;
+    if (sp.fits) {                                          // W^T fits LDS twice per CU
         const uint32_t need = (n_query + kAnsWaves * qpw - 1) / (kAnsWaves * qpw);
         auto go = [&](auto kernel, auto kernel_topk) {      // persistent: two 16-wavefront workgroups per CU
             const QmPersistent wg{kAnsWaves, 8};
@@ -881,9 +919,9 @@ static int answer_f32_impl(const qmann_net *net, const float *w_ans, const float
         return qm_scope.rc();
     }
     const uint32_t grid = n_query < 8192u ? n_query : 8192u;
-    if (tk) qm_launch(k_answer<false, true>, grid, kBlock, lds, st, w_ans, u, answer, pred, probs, cost, match, D, V, net->softmax_base, n_query, *tk);
+    if (tk) qm_launch(k_answer<false, true>, grid, kBlock, lds, st, w_ans, u, answer, pred, probs, cost, match, D, V, net->softmax_base, n_query, 0u, 0u, *tk);
     else qm_launch(k_answer<false>, grid, kBlock, lds, st,
-              w_ans, u, answer, pred, probs, cost, match, D, V, net->softmax_base, n_query, AnsTopK<false>{});
+              w_ans, u, answer, pred, probs, cost, match, D, V, net->softmax_base, n_query, 0u, 0u, AnsTopK<false>{});
     QM_LAUNCH_CHECK();
     return qm_scope.rc();
 }
@@ -926,14 +964,16 @@ int qmann_answer_i8(const qmann_net *net, const int8_t *w_ans_i8, qmann_fmt w_fm
     const float scale = 1.0f / (float)(1u << (fu.frac + w_fmt.frac));
     hipStream_t st = (hipStream_t)stream;
     const QFmt fuq = qm_qfmt(fu);
-    // (the running-maximum normaliser needs a true exponential: the piece-wise linear exp_plan takes the two-pass form)
-    if (!probs && net->softmax_base != QMANN_SOFTMAX_EXP_PLAN && !qm_tuning().answer_two_pass) {
+    // (the running-maximum normaliser needs a true exponential: the piece-wise linear exp_plan takes the two-pass form; so does a
+    // dictionary of 1, 2 or 3 answers, whose documented workspace of V floats per query is smaller than one record)
+    const bool records_fit = (size_t)V * sizeof(float) >= sizeof(AnsPart);
+    if (!probs && net->softmax_base != QMANN_SOFTMAX_EXP_PLAN && !qm_tuning().answer_two_pass && records_fit) {
         // one pass: no logits round trip; the workspace holds the per-slice records
         const uint32_t qblocks = (n_query + 16 * kWaves - 1) / (16 * kWaves), n_tiles = (V + kAnsTile - 1) / kAnsTile;
         // ~2 workgroups per CU (measured at 8 192 x 4 096 x 256: 128 workgroups 86 us, 256: 55, 512: 45, 1 024: 46)
         uint32_t n_slice = qblocks >= 512u ? 1u : (512u + qblocks - 1) / qblocks;
         if (n_slice > n_tiles) n_slice = n_tiles;
-        while (n_slice > 1 && (size_t)n_slice * sizeof(AnsPart) > (size_t)V * sizeof(float)) n_slice--;   // records must fit logits_ws
+        // the records fit logits_ws: V >= 4 here, and n_slice <= ceil(V / 64) gives 16 n_slice <= 4 V bytes per query
         const uint32_t tps = (n_tiles + n_slice - 1) / n_slice;
         n_slice = (n_tiles + tps - 1) / tps;
         AnsPart *part = (AnsPart *)logits_ws;
@@ -957,8 +997,11 @@ int qmann_answer_i8(const qmann_net *net, const int8_t *w_ans_i8, qmann_fmt w_fm
             k_logits_mfma_i8<decltype(dp)::value / 64><<<grid, kBlock, 0, st>>>(u, w_ans_i8, logits_ws, n_query, D, V, fuq, scale);
         }))
         return QMANN_EUNSUPPORTED;
+    // the normaliser in the order of the float layer's kernel for this shape: probabilities bit-identical to it (see k_answer)
+    const AnsSmallPlan sp = ans_small_plan(D, V);
     qm_launch(k_answer<true>, n_query < 8192u ? n_query : 8192u, kBlock, lds, st,
-              logits_ws, nullptr, answer, pred, probs, cost, match, D, V, net->softmax_base, n_query, AnsTopK<false>{});
+              logits_ws, nullptr, answer, pred, probs, cost, match, D, V, net->softmax_base, n_query,
+              sp.fits ? sp.lpq : 0u, sp.lpq == 64u ? 4u : sp.vpt, AnsTopK<false>{});
     QM_LAUNCH_CHECK();
     return qm_scope.rc();
 }
