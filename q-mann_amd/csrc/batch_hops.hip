@@ -27,14 +27,64 @@
 //   4. linear map H.u (int8 [D][Dp], L2-resident) and u' = Q(Q(Hu) + Q(o)).
 //
 // All integer work is exact; the only floating-point step is the softmax table.
+//
+//   1b. (the STOP instantiation: e^x softmax, no taps, a bound some hop can reach -- hops_host.h::scan_stop_gate)  While it
+//      scans, the workgroup also sums e^(x_r - Xb) over the rows retired so far, Xb the largest score the attention format
+//      can hold.  Once that sum passes 2^frac (1 + 2^-6) every read-out weight of the hop is known to quantise to code 0
+//      whatever the unread rows hold (derivation: ScanStop below): the wavefronts leave the scan, steps 2 and 3 are skipped
+//      and the hop continues with o = 0, the result the full scan would have produced.
 #include "hops_mid.h"
 #include "hops_host.h"
 
 namespace {
 
+// Tiles a wavefront retires between two looks at the workgroup's running sum (even; another value: tools/build_variant.sh)
+constexpr uint32_t kStopCadence = 4;
+static_assert(kStopCadence >= 2 && kStopCadence % 2 == 0, "scan_rows asks its hook every two tiles");
+
+// Why a hop's key scan may end early.  The e^x softmax gives slot r the weight p_r = (float)(e_r / total), e_r =
+// expf(x_r - xmax) <= 1 and total = sum_r e_r in double (hops_common.h::sm_quot).  qm_code (qfmt.h) truncates p . 2^frac toward
+// zero, so p_r < 2^-frac is weight code 0; with e_r <= 1 that holds for EVERY slot as soon as total > 2^frac, and the read-out
+// is then exactly 0 (readout_sparse with no surviving row).  Scores are clamped to the attention format, so whatever the unread
+// rows hold, xmax <= Xb = max(sm_scaled(+maxm / 2^frac_m), sm_scaled(-maxm / 2^frac_m)) (the second term for a negative scale
+// layer; sm_scaled is one float product, monotone in the code), and over any set P of rows already retired
+//     total >= sum_{r in P} e^(x_r - xmax) >= sum_{r in P} e^(x_r - Xb).
+// The sum on the right is what the scan accumulates -- in float, one v_exp_f32 per row (1 ulp, arguments <= 0, a flushed
+// denormal only lowers it), at most a few 10^4 additions (each within 6e-8 relative, 6e-4 in all even if every one rounded up) and
+// an exponent folded into one FMA (argument off by < 2e-5): the threshold 2^frac (1 + 2^-6) leaves 1.5 %, some twenty times
+// those errors together, and puts 1 / total far enough below 2^-frac that the float quotient cannot round up to it.  A NaN or
+// infinite scale makes the sum NaN, which never compares >= thr: such a hop runs the full path.
+// Each wavefront adds its lanes' sums to one LDS float every kStopCadence tiles (a returning LDS add: it sees the workgroup's
+// sum so far) and leaves when that has passed thr.  The sum only grows, so the other wavefronts follow within one cadence, and
+// the workgroup's decision behind the scan's barrier -- the same LDS word, read by all -- is "zero" whenever any wavefront left.
+struct ScanStop {
+    float &lane_sum;          // this lane's e^(x_r - Xb) since the last flush (the retire hook adds to it)
+    float *word;              // the workgroup's sum (LDS)
+    float thr;
+    uint32_t lane, n;
+    // the lanes' sums into the workgroup's; every lane returns the workgroup's sum including them
+    __device__ __forceinline__ float flush()
+    {
+        float v = lane_sum;
+        lane_sum = 0.0f;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+        float tot = 0.0f;
+        if (lane == 0) tot = atomicAdd(word, v) + v;
+        return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, tot)));
+    }
+    __device__ __forceinline__ bool operator()()
+    {
+        if (++n < kStopCadence / 2) return false;
+        n = 0;
+        return flush() >= thr;
+    }
+};
+
 // W7: every attention format of the launch has word length 7 -- the clamp comes from the signed saturation of the
 // multiply and the quotient is a byte gather (hops_common.h::lane_row_sum7): 9 instead of 11 operations per 4 key bytes
-template <int LPR, int kUnroll, bool NT, int MINW, bool W7>
+// STOP: step 1b of the header (four-wavefront launches only)
+template <int LPR, int kUnroll, bool NT, int MINW, bool W7, bool STOP = false>
 __global__ void __launch_bounds__(kBlock, MINW)
 k_hops_fixed(const HopArgs a)
 {
@@ -74,6 +124,18 @@ k_hops_fixed(const HopArgs a)
             for (uint32_t i = 0; i < nwaves; i++) hist[i * 256 + c] = 0u;
         }
         if (tid == 0) misc[0] = 0u;
+        // the bound of step 1b: e^(x - Xb) = 2^(code . stop_k1 + stop_k0)
+        float *stop_word = (float *)(misc + 1);
+        float stop_thr = 0.0f, stop_k1 = 0.0f, stop_k0 = 0.0f, stop_sum = 0.0f;
+        if constexpr (STOP) {
+            const SmCfg smc = sm_cfg(a, h);
+            const float top = qm_scale_down((float)maxm, fm.frac), log2e = 1.44269504f;
+            const float xb = fmaxf(sm_scaled(top, smc), sm_scaled(-top, smc));
+            stop_k1 = sm_scaled(qm_scale_down(1.0f, fm.frac), smc) * log2e;
+            stop_k0 = -xb * log2e;
+            stop_thr = (float)(1u << fa.frac) * (1.0f + 0.015625f);
+            if (tid == 0) stop_word[0] = 0.0f;
+        }
         __syncthreads();
 
         if (S > 0) {
@@ -89,16 +151,25 @@ k_hops_fixed(const HopArgs a)
                 const int code = v > maxm ? maxm : (v < -maxm ? -maxm : v);
                 sc[r] = (int8_t)code;
                 atomicAdd(&hw[code + 127], 1u);
+                if constexpr (STOP) stop_sum += __builtin_amdgcn_exp2f(__builtin_fmaf((float)code, stop_k1, stop_k0));
             };
             if (S < (kWave / LPR) * kUnroll) scan_rows_short<LPR>(kb, S, row_sum, retire, lane, wave, nwaves);
-            else if (nwaves == kWaves) scan_rows<LPR, kUnroll, NT, kWaves>(kb, S, row_sum, retire, lane, wave);
+            else if (nwaves == kWaves) {
+                if constexpr (STOP) scan_rows<LPR, kUnroll, NT, kWaves>(kb, S, row_sum, retire, lane, wave, ScanStop{stop_sum, stop_word, stop_thr, lane, 0u});
+                else scan_rows<LPR, kUnroll, NT, kWaves>(kb, S, row_sum, retire, lane, wave);
+            }
             else scan_rows<LPR, kUnroll, NT, 1>(kb, S, row_sum, retire, lane, wave);
+            // what the lanes still hold: the decision below is taken on the whole sum, whether or not a wavefront left early
+            if constexpr (STOP) (void)ScanStop{stop_sum, stop_word, stop_thr, lane, 0u}.flush();
         }
         __syncthreads();
+        // every weight code of this hop is 0 (ScanStop above): no softmax, no survivors, o = 0.  All threads read the one word.
+        bool all_zero = false;
+        if constexpr (STOP) all_zero = stop_word[0] >= stop_thr;
 
         // softmax over slots from the histogram of score codes (bin d <-> code d - 127)
         uint32_t n_live = 0;
-        if (S > 0) {
+        if (S > 0 && !all_zero) {
             // each thread owns bins tid, tid + nthreads, ... (4 bins per thread in a one-wavefront group)
             const SmCfg smc = sm_cfg(a, h);
             auto bin_x = [&](uint32_t d) { return sm_scaled(qm_scale_down((float)((int)d - 127), fm.frac), smc); };
@@ -279,7 +350,11 @@ int qm_hops_i8(const qmann_net *net, const int8_t *keys, const int8_t *vals, siz
             // as many queries resident per CU and no cross-wavefront barriers
             const dim3 block(max_slots <= 256 ? kWave : kBlock);
             // (bounding the kernel to 96 VGPRs for a fifth wavefront per SIMD measured 1-3 % slower: MINW stays 1)
-            qm_dispatch<false, true>(w7, [&](auto w) { qm_launch(k_hops_fixed<LPR, kUnrollDefault, true, 1, decltype(w)::value>, n_query, block, lds, st, a); });
+            // (step 1b of the header: only where some hop's bound lies within the memory; every other launch keeps its kernel)
+            if (block.x == (unsigned)kBlock && !qm_tuning().no_scan_stop && scan_stop_gate(a, max_slots))
+                qm_dispatch<false, true>(w7, [&](auto w) { qm_launch(k_hops_fixed<LPR, kUnrollDefault, true, 1, decltype(w)::value, true>, n_query, block, lds, st, a); });
+            else
+                qm_dispatch<false, true>(w7, [&](auto w) { qm_launch(k_hops_fixed<LPR, kUnrollDefault, true, 1, decltype(w)::value>, n_query, block, lds, st, a); });
         });
     });
     QM_LAUNCH_CHECK();

@@ -263,12 +263,17 @@ __device__ __forceinline__ void scan_rows_short(const uint8_t *__restrict__ kb, 
     }
 }
 
+// scan_rows' stop hook when the caller has none: no code
+struct ScanNoStop {};
+
 // One wavefront streams tiles of UN x (64 / LPR) rows; loads of the next tile are issued before
 // the current one is reduced (addresses are clamped to the last row instead of being predicated,
 // so the loop body has no divergent control flow and the compiler can count its vmcnt waits).
-template <int LPR, int UN, bool NT, int NW, typename RowSum, typename Retire>
+// `stop`: asked once per loop iteration (two tiles retired); a wavefront-uniform true ends this wavefront's scan -- the tile
+// already requested is dropped (its addresses were in range like every other tile's).  The hook keeps its own cadence.
+template <int LPR, int UN, bool NT, int NW, typename RowSum, typename Retire, typename Stop = ScanNoStop>
 __device__ __forceinline__ void scan_rows(const uint8_t *__restrict__ kb, uint32_t S, RowSum row_sum, Retire retire,
-                                          uint32_t lane, uint32_t wave)
+                                          uint32_t lane, uint32_t wave, Stop stop = Stop{})
 {
     constexpr uint32_t nwaves = NW;                // wavefronts sharing the rows of this query
     constexpr uint32_t RPW = kWave / LPR;          // rows per wavefront instruction
@@ -317,6 +322,8 @@ __device__ __forceinline__ void scan_rows(const uint8_t *__restrict__ kb, uint32
         issue(xa, base + 2 * STEP);
         reduce(xb, base + STEP);
         base += 2 * STEP;
+        if constexpr (!std::is_same<Stop, ScanNoStop>::value)
+            if (stop()) break;
     }
 }
 

@@ -71,6 +71,26 @@ inline int fill_hop_args(HopArgs &a, const qmann_net *net, const void *keys, con
     return QMANN_OK;
 }
 
+// May the fixed-point hop kernel end a key scan early (batch_hops.hip, step 1b and ScanStop)?  Only the e^x softmax without the
+// shift, only without taps (they need every score), and only where for at least one hop the bound can be reached inside the
+// memory at all: a hop's scan sums e^(x_r - Xb) <= 1 per row and stops at 2^frac (1 + 2^-6), so even a memory of all-zero scores
+// (e^x = 1) needs 2^frac . e^Xb . (1 + 2^-6) rows.  Xb as the kernel forms it (one float product for the scale layer), the rest
+// in double; a NaN scale compares false.  Q2.5 wants 1 720 rows, Q5.2 4 e^31.75: such a launch keeps the plain kernel.
+inline bool scan_stop_gate(const HopArgs &a, uint32_t max_slots)
+{
+    if (a.tap_codes || a.tap_scores || a.tap_probs || a.tap_o || a.tap_u) return false;
+    if (a.softmax_base != QMANN_SOFTMAX_EXP || a.softmax_shift != 0) return false;
+    for (uint32_t h = 0; h < a.n_hop; h++) {
+        const QFmt fm = a.att[h], fa = a.act[h];
+        const float top = qm_scale_down((float)((1u << (fm.iwl + fm.frac)) - 1u), fm.frac);
+        const float pos = a.en_att_scale ? top * a.att_scale[h] : top, neg = a.en_att_scale ? -top * a.att_scale[h] : -top;
+        const double xb = pos > neg ? (double)pos : (double)neg;                 // (NaN: neg, and the compare below is false)
+        const double rows = (double)(1u << fa.frac) * exp(xb) * (1.0 + 0.015625);
+        if (rows <= (double)max_slots) return true;
+    }
+    return false;
+}
+
 // The ONE decision of a hop launch: the form it takes.  No HIP call, no state but qm_tuning(): asking twice gives the same
 // answer, which is how the host model knows ahead of the launch that a batch will be split (batch_hops.hip::qm_hops_will_split).
 // Up to 64 slots the lean kernels where they cover the call -- not for packed planes, which have no lean form -- else one

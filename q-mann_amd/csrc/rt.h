@@ -63,6 +63,7 @@ struct QmTuning {
     bool no_corun;                                    // QMANN_NO_CORUN: no second stream (the two hop kernels of a split batch, the question embedding beside the story embedding: in sequence)
     bool no_quad;                                     // QMANN_NO_QUAD: short stories keep the one-wavefront-per-query kernel (hops_quad.h off)
     bool no_tight;                                    // QMANN_NO_TIGHT (set, any value): the lean kernels keep their four-wave (128-register) builds
+    bool no_scan_stop;                                // QMANN_NO_SCAN_STOP (set, any value): the fixed-point hop kernel scans every key row even where the read-out is already known to be zero (batch_hops.hip, step 1b)
     int lean_sparse;                                  // -1 = the launcher chooses, 0 / 1 forced
     uint32_t shared_qt;                               // QMANN_SHARED_QT (1, 2, 4 or 8): queries per workgroup of qmann_hops_shared_i8 where they fit in LDS; 0 = the launcher chooses
     uint32_t quad_min_queries;                        // QMANN_QUAD_MIN_QUERIES (default 8192): batches of at most this many stories keep one story per wavefront (hops_lean.h)

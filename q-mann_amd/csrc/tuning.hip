@@ -36,6 +36,7 @@ void read_env(QmTuning &t)
         t.shared_qt = (v == 1 || v == 2 || v == 4 || v == 8) ? (uint32_t)v : 0u;     // (anything else: the launcher chooses)
     }
     t.no_tight = on("QMANN_NO_TIGHT");              // presence-only, like its siblings
+    t.no_scan_stop = on("QMANN_NO_SCAN_STOP");
 }
 
 }  // namespace
