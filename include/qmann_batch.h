@@ -210,6 +210,32 @@ int qmann_hops_shared_split_top_i8(const qmann_net *net, const int8_t *keys, con
                                    uint32_t *top_slot, float *top_p, uint32_t n_query, uint32_t n_slices,
                                    void *ws, size_t ws_bytes, void *stream);
 
+/* Attended slots per story: qmann_hops_i8 (every query its OWN memory) that also returns, per query and hop, the k rows of the
+ * query's story the hop weighted most and their weights, without a [n_hop][rows_total] probability array anywhere.
+ *   top_slot [n_query][n_hop][k] uint32, top_p [n_query][n_hop][k] float, device memory; 1 <= k <= QMANN_MAX_TOP_SLOTS.
+ * In terms of what qmann_hops_i8 writes to taps.probs for the same arguments, with r0 = row_off[q] and S = min(row_off[q+1] - r0,
+ * max_slots): row (q, h) lists the slots s in [0, S) -- counted from the story's first row -- that come first in the order
+ * "larger probability first, equal probabilities: lower slot first", and top_p[q][h][j] is bit-equal to
+ * probs[h][r0 + top_slot[q][h][j]].  The order is over the probability VALUES, as floats (slots whose scores differ tie where
+ * their probabilities are equal; a negative att_scale needs no rule of its own); a NaN probability ranks below every number.
+ * Entries past S hold slot 0xFFFFFFFF and p 0.0f: an empty story, k > S, a story cut by max_slots (no slot >= max_slots appears).
+ * u_out is bit-equal to that of qmann_hops_i8 called with taps on the same arguments, and every qmann_net field the base call
+ * honours is honoured.  hop_stride = 0 (tied hops) is allowed -- the outputs are indexed by query, not by plane row -- and gives
+ * the result of the call on n_hop copies of the plane.  There is no taps argument.
+ * Served: QMANN_ATT_FIXED at every length the base call takes (up to its LDS cap); QMANN_ATT_APPX (EN_MQ's operand grids
+ * included) and QMANN_ATT_HAMMING_V0 / _V1 on int8 keys up to max_slots = 64, which covers every bAbI story.  The selection runs
+ * inside the kernels a call with taps launches (csrc/hops_attended_story.h): in registers of the one-wavefront kernel up to 64
+ * slots, from the score histogram and the score bytes of the streaming fixed-point kernel beyond (which never ends a scan early
+ * for such a call: the selection needs every score).
+ * Nothing is launched, no output is touched and the code returned is: whatever qmann_hops_i8 answers for the same arguments
+ * without taps, unchanged and FIRST (its refusals; n_query = 0 is QMANN_OK whatever k); then QMANN_EUNSUPPORTED for
+ * QMANN_ATT_FLOAT at any length and for QMANN_ATT_APPX / _HAMMING_V0 / _V1 with max_slots > 64; then QMANN_EINVAL for k = 0,
+ * k > QMANN_MAX_TOP_SLOTS, a null top_slot or top_p.
+ * One kernel on `stream`: no second stream, no library scratch, no allocation -- it can be captured in a graph. */
+int qmann_hops_top_i8(const qmann_net *net, const int8_t *keys, const int8_t *vals, size_t hop_stride,
+                      const uint32_t *row_off, uint32_t max_slots, const float *u0, float *u_out,
+                      uint32_t k, uint32_t *top_slot, float *top_p, uint32_t n_query, void *stream);
+
 /* Packed binary codes for the Hamming forms: sign-magnitude bytes [rows][Dp] -> bit planes
  * uint64 [rows][Dp/64][num_bit] (plane 0 = sign bits, plane i = magnitude bit 7-i; bit b of a word
  * is column 64.g + b).  num_bit in 1..8.  sm_codes 16-byte aligned, planes 8-byte aligned (QMANN_EINVAL otherwise). */

@@ -91,6 +91,23 @@ int qmann_model_forward_words(qmann_model *m, const uint16_t *story_words, uint3
                               uint32_t max_slots, uint32_t n_query, const uint32_t *answer, uint32_t *pred,
                               float *cost, uint32_t *match, void *stream);
 
+/* qmann_model_forward_words that also returns the attended slots of every question and hop: top_slot uint32 / top_p float
+ * [n_query][n_hop][k], device memory, the rows qmann_hops_top_i8 (qmann_batch.h) defines -- the k rows of the question's own
+ * story each hop weighted most, counted from the story's first row, larger probability first, equal probabilities: lower row
+ * first; past the story's length (cut to max_slots) slot 0xFFFFFFFF and p 0.  It embeds exactly as qmann_model_forward_words
+ * does (the question embedding beside the story embedding for large batches), runs the hops through qmann_hops_top_i8 on the
+ * model's int8 keys (one plane when the model is tied; the packed-plane route is never taken) and the same answer layer:
+ * pred, cost, match, qmann_model_last_u and what qmann_model_last_topk ranks are those of qmann_model_forward_words.  It
+ * allocates nothing once the workspace has its size, so it can be captured in a graph and replayed.
+ * What qmann_model_forward_words refuses or answers without work is answered FIRST and as there (null model: QMANN_EINVAL;
+ * n_query = 0: QMANN_OK whatever k; null question_words, row_off or pred: QMANN_EINVAL); then QMANN_EUNSUPPORTED for a float
+ * model, and for max_slots > 64 on a model that is not fixed-point; then QMANN_EINVAL for k = 0, k > QMANN_MAX_TOP_SLOTS, a
+ * null top_slot or top_p.  Such a call launches nothing and leaves every output as it was. */
+int qmann_model_forward_words_top(qmann_model *m, const uint16_t *story_words, uint32_t rows_total, uint32_t max_words,
+                                  const uint16_t *question_words, uint32_t max_q_words, const uint32_t *row_off,
+                                  uint32_t max_slots, uint32_t n_query, const uint32_t *answer, uint32_t *pred,
+                                  float *cost, uint32_t *match, uint32_t k, uint32_t *top_slot, float *top_p, void *stream);
+
 /* One story, many questions: story_words [n_rows][max_words] is embedded ONCE (every hop, or one plane when the hops are tied)
  * and all n_query questions attend to it.  Same results as qmann_model_forward_words on n_query copies of the story.
  * The workspace holds n_rows rows of memory, not n_query x n_rows.  Attention mode QMANN_ATT_FIXED only (what

@@ -160,6 +160,8 @@ _proto("qmann_check_slots", C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, _vp])
 _proto("qmann_quantize_i8", C.c_int, [_vp, _vp, C.c_size_t, C.c_uint32, C.c_uint32, Fmt, C.c_int, _vp])
 _proto("qmann_hops_i8", C.c_int, [C.POINTER(Net), _vp, _vp, C.c_size_t, _vp, C.c_uint32, _vp, _vp,
                                   C.POINTER(Taps), C.c_uint32, _vp])
+_proto("qmann_hops_top_i8", C.c_int, [C.POINTER(Net), _vp, _vp, C.c_size_t, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp,
+                                      C.c_uint32, _vp])
 _proto("qmann_hops_shared_lds_bytes", C.c_size_t, [C.c_uint32, C.c_uint32])
 _proto("qmann_hops_shared_tile", C.c_uint32, [C.c_uint32, C.c_uint32])
 _proto("qmann_hops_shared_i8", C.c_int, [C.POINTER(Net), _vp, _vp, C.c_size_t, C.c_uint32, _vp, _vp,
@@ -226,6 +228,8 @@ _proto("qmann_comm_broadcast", C.c_int, [_vp, C.c_int, _vp, C.c_size_t, _vp])
 _proto("qmann_comm_allgather_u32", C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp])
 _proto("qmann_model_forward_words", C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _vp, C.c_uint32, _vp, C.c_uint32,
                                               C.c_uint32, _vp, _vp, _vp, _vp, _vp])
+_proto("qmann_model_forward_words_top", C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _vp, C.c_uint32, _vp, C.c_uint32,
+                                                  C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp])
 _proto("qmann_model_forward_shared_words", C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _vp, C.c_uint32, C.c_uint32,
                                                      _vp, _vp, _vp, _vp, _vp])
 _proto("qmann_model_memorize_words", C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _vp])

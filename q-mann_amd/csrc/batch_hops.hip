@@ -84,10 +84,13 @@ struct ScanStop {
 // W7: every attention format of the launch has word length 7 -- the clamp comes from the signed saturation of the
 // multiply and the quotient is a byte gather (hops_common.h::lane_row_sum7): 9 instead of 11 operations per 4 key bytes
 // STOP: step 1b of the header (four-wavefront launches only)
-template <int LPR, int kUnroll, bool NT, int MINW, bool W7, bool STOP = false>
+// TOP: the attended slots of every hop besides (hops_attended_story.h::story_select_hist, behind finish_hop); never with STOP,
+// the selection needs every score
+template <int LPR, int kUnroll, bool NT, int MINW, bool W7, bool STOP = false, bool TOP = false>
 __global__ void __launch_bounds__(kBlock, MINW)
-k_hops_fixed(const HopArgs a)
+k_hops_fixed(const HopArgs a, const StoryTop<TOP> tp)
 {
+    static_assert(!(STOP && TOP), "a hop that ends its scan early has no histogram to select from");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     uint32_t *hist = (uint32_t *)(smem + kOffHist);
     float *ptab = (float *)(smem + kOffPtab);
@@ -228,6 +231,7 @@ k_hops_fixed(const HopArgs a)
         // weighted read-out over the surviving rows, linear map, hop update (hops_common.h)
         auto kp_of_row = [&](uint32_t r) { return (int)kplut[(int)sc[r] + 127]; };
         finish_hop<Dp>(a, q, h, r0, S, n_live, live_row, live_kp, kp_of_row, ku, u_f, o_f, tid);
+        if constexpr (TOP) story_select_hist(tp, (size_t)q * a.n_hop + h, S, hist, ptab, sc, live_row, live_kp, misc, red, tid, lane, wave);
     }
     for (uint32_t c = tid; c < D; c += nthreads) a.u_out[(size_t)q * D + c] = relu_if(u_f[c], a.en_non_lin != 0);
 }
@@ -337,8 +341,12 @@ int qm_hops_i8(const qmann_net *net, const int8_t *keys, const int8_t *vals, siz
     if (n_query == 0) return QMANN_OK;
     if (qm_too_many_queries(n_query)) return QMANN_ERANGE;
 
-    if (net->attention_mode == QMANN_ATT_FLOAT)
+    if (net->attention_mode == QMANN_ATT_FLOAT) {
+        // (attended slots: float attention is not served -- behind the one refusal the float launcher has of its own)
+        if (hints.top_on) return (size_t)kOffScores + (((size_t)max_slots * 4 + 15) & ~(size_t)15) > 160 * 1024 - 1024 ? QMANN_ERANGE : QMANN_EUNSUPPORTED;
         return qmann_hops_float_impl(a, net->dim_emb_pad, max_slots, n_query, stream);
+    }
+    if (hints.top_on && !story_top_args_ok(hints.top_k, hints.top_slot, hints.top_p)) return QMANN_EINVAL;     // behind every refusal of the base call
 
     hipStream_t st = (hipStream_t)stream;
     const bool w7 = !qm_tuning().no_w7 && all_w7(a, kW7Att);
@@ -349,12 +357,17 @@ int qm_hops_i8(const qmann_net *net, const int8_t *keys, const int8_t *vals, siz
             // memories of 65..256 slots run one wavefront per query with the histogram softmax: four times
             // as many queries resident per CU and no cross-wavefront barriers
             const dim3 block(max_slots <= 256 ? kWave : kBlock);
+            if (hints.top_on) {                             // (the plain kernel's block at every length: p is the tap's, bit for bit)
+                const StoryTop<true> tp{hints.top_slot, hints.top_p, hints.top_k};
+                qm_dispatch<false, true>(w7, [&](auto w) { qm_launch(k_hops_fixed<LPR, kUnrollDefault, true, 1, decltype(w)::value, false, true>, n_query, block, lds, st, a, tp); });
+                return;
+            }
             // (bounding the kernel to 96 VGPRs for a fifth wavefront per SIMD measured 1-3 % slower: MINW stays 1)
             // (step 1b of the header: only where some hop's bound lies within the memory; every other launch keeps its kernel)
             if (block.x == (unsigned)kBlock && !qm_tuning().no_scan_stop && scan_stop_gate(a, max_slots))
-                qm_dispatch<false, true>(w7, [&](auto w) { qm_launch(k_hops_fixed<LPR, kUnrollDefault, true, 1, decltype(w)::value, true>, n_query, block, lds, st, a); });
+                qm_dispatch<false, true>(w7, [&](auto w) { qm_launch(k_hops_fixed<LPR, kUnrollDefault, true, 1, decltype(w)::value, true>, n_query, block, lds, st, a, StoryTop<false>{}); });
             else
-                qm_dispatch<false, true>(w7, [&](auto w) { qm_launch(k_hops_fixed<LPR, kUnrollDefault, true, 1, decltype(w)::value>, n_query, block, lds, st, a); });
+                qm_dispatch<false, true>(w7, [&](auto w) { qm_launch(k_hops_fixed<LPR, kUnrollDefault, true, 1, decltype(w)::value>, n_query, block, lds, st, a, StoryTop<false>{}); });
         });
     });
     QM_LAUNCH_CHECK();
@@ -365,4 +378,14 @@ extern "C" int qmann_hops_i8(const qmann_net *net, const int8_t *keys, const int
                              uint32_t max_slots, const float *u0, float *u_out, const qmann_taps *taps, uint32_t n_query, void *stream)
 {
     return qm_hops_i8(net, keys, vals, hop_stride, row_off, max_slots, u0, u_out, taps, n_query, stream, QmHopHints{});
+}
+
+// qmann_hops_i8 without taps plus the attended slots of every hop: one kernel on `stream` (hops_attended_story.h)
+extern "C" int qmann_hops_top_i8(const qmann_net *net, const int8_t *keys, const int8_t *vals, size_t hop_stride, const uint32_t *row_off,
+                                 uint32_t max_slots, const float *u0, float *u_out, uint32_t k, uint32_t *top_slot, float *top_p,
+                                 uint32_t n_query, void *stream)
+{
+    QmHopHints hints;
+    hints.top_on = true; hints.top_k = k; hints.top_slot = top_slot; hints.top_p = top_p;
+    return qm_hops_i8(net, keys, vals, hop_stride, row_off, max_slots, u0, u_out, nullptr, n_query, stream, hints);
 }

@@ -299,6 +299,15 @@ int ham_prepare(HopArgs &a, size_t &lds, const qmann_net *net, const void *keys,
     return kHamGo;
 }
 
+// Attended slots per story (qmann_hops_top_i8, hints.top_on) in this family: the one-wavefront kernel only, so memories beyond 64
+// slots are refused; then the call's own arguments.  Behind every refusal of the base call (ham_prepare).
+int ham_top_check(const QmHopHints &hints, uint32_t max_slots)
+{
+    if (!hints.top_on) return QMANN_OK;
+    if (max_slots > (uint32_t)kWave) return QMANN_EUNSUPPORTED;
+    return story_top_args_ok(hints.top_k, hints.top_slot, hints.top_p) ? QMANN_OK : QMANN_EINVAL;
+}
+
 // lean / small (hops_host.h::launch_hops) for one attention mode of the family, k_hops_ham for memories beyond 64 slots
 template <int MODE, int NB, int DP, int LPRK>
 void launch_ham(const HopArgs &a, size_t lds, uint32_t max_slots, uint32_t n_query, hipStream_t st, const QmHopHints &hints)
@@ -336,6 +345,7 @@ int qmann_hops_appx_impl(const qmann_net *net, const int8_t *keys, const int8_t 
     HopArgs a;
     size_t lds;
     if (const int rc = ham_prepare(a, lds, net, keys, vals, hop_stride, hop_stride, row_off, max_slots, u0, u_out, taps, n_query, hints); rc != kHamGo) return rc;
+    if (const int rc = ham_top_check(hints, max_slots)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const bool mq = a.ham_kinds != 0;                       // some hop's operands leave the attention grid (EN_MQ): the kernels
                                                             // that carry all three lane sums (ham_common.h)
@@ -358,6 +368,7 @@ int qmann_hops_hambytes_impl(const qmann_net *net, const int8_t *keys, const int
     HopArgs a;
     size_t lds;
     if (const int rc = ham_prepare(a, lds, net, keys, vals, hop_stride, hop_stride, row_off, max_slots, u0, u_out, taps, n_query, hints); rc != kHamGo) return rc;
+    if (const int rc = ham_top_check(hints, max_slots)) return rc;
     const bool v1 = net->attention_mode == QMANN_ATT_HAMMING_V1;
     hipStream_t st = (hipStream_t)stream;
     qm_dispatch<64, 128, 256>(Dp, [&](auto dp) {

@@ -95,14 +95,16 @@ inline bool scan_stop_gate(const HopArgs &a, uint32_t max_slots)
 // answer, which is how the host model knows ahead of the launch that a batch will be split (batch_hops.hip::qm_hops_will_split).
 // Up to 64 slots the lean kernels where they cover the call -- not for packed planes, which have no lean form -- else one
 // wavefront per query; longer memories: hops_mid.h where it covers them, else the family's general kernel.
-inline HopPlan hop_plan(const HopArgs &a, int mode, uint32_t key_row_bytes, uint32_t max_slots, uint32_t n_query)
+// `every_prob`: the call wants every slot's probability without a tap in HopArgs (attended slots per story, qmann_hops_top_i8):
+// it plans as a call with taps does -- one wavefront per query up to 64 slots, the general kernel beyond.
+inline HopPlan hop_plan(const HopArgs &a, int mode, uint32_t key_row_bytes, uint32_t max_slots, uint32_t n_query, bool every_prob = false)
 {
     // (known from the plane size; tied hops without a hint carry none and take the bAbI guess: stories short next to their cap)
     const uint32_t mean_slots = (a.rows_total && n_query) ? a.rows_total / n_query : max_slots / 8u;
     auto plan = [&](HopForm f) { return HopPlan{f, mean_slots}; };
-    if (mode_is_planes(mode) || !lean_supported(a, max_slots, key_row_bytes)) {
+    if (every_prob || mode_is_planes(mode) || !lean_supported(a, max_slots, key_row_bytes)) {
         if (max_slots <= (uint32_t)kWave) return plan(HopForm::Small);
-        return plan(mode == kModeFixed && mid_supported(a, max_slots) ? HopForm::Mid : HopForm::General);    // hops_mid.h: 65 .. 1 024 slots at bAbI width
+        return plan(mode == kModeFixed && !every_prob && mid_supported(a, max_slots) ? HopForm::Mid : HopForm::General);    // hops_mid.h: 65 .. 1 024 slots at bAbI width
     }
     // Small batches keep one story per wavefront: the GPU holds 6 144 wavefronts at once, so up to a few thousand stories each has
     // one of its own and the batch takes ONE story's latency, where four stories per wavefront take their linear maps in turn
@@ -126,12 +128,20 @@ template <int MODE, int NB, int LPR, int LPRK, typename General>
 inline void launch_hops(const HopArgs &a, uint32_t max_slots, uint32_t n_query, hipStream_t st, const QmHopHints &hints, General &&general)
 {
     constexpr uint32_t key_row_bytes = 16u * LPRK;
-    const HopPlan plan = hop_plan(a, MODE, key_row_bytes, max_slots, n_query);
+    const HopPlan plan = hop_plan(a, MODE, key_row_bytes, max_slots, n_query, hints.top_on);
     switch (plan.form) {
     case HopForm::Lean: case HopForm::Quad: case HopForm::QuadLong: case HopForm::Split:
         if constexpr (!mode_is_planes(MODE)) launch_lean<MODE, NB>(a, plan, max_slots, n_query, st, hints.split_ws);
         break;
-    case HopForm::Small: k_hops_small<LPR, LPRK, MODE, NB><<<n_query, kWave, 0, st>>>(a, key_row_bytes); break;
+    case HopForm::Small:
+        if constexpr (!mode_is_planes(MODE)) {              // (attended slots per story: int8 keys only)
+            if (hints.top_on) {
+                k_hops_small<LPR, LPRK, MODE, NB, true><<<n_query, kWave, 0, st>>>(a, key_row_bytes, StoryTop<true>{hints.top_slot, hints.top_p, hints.top_k});
+                break;
+            }
+        }
+        k_hops_small<LPR, LPRK, MODE, NB><<<n_query, kWave, 0, st>>>(a, key_row_bytes, StoryTop<false>{});
+        break;
     case HopForm::Mid: case HopForm::General: general(plan.form); break;
     }
 }

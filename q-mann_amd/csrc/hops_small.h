@@ -4,15 +4,17 @@
 // arithmetic as the streaming kernels (batch_hops.hip, batch_hops_ham.hip); MODE selects the score.
 #pragma once
 #include "ham_common.h"
+#include "hops_attended_story.h"
 
 namespace {
 
 enum { kModeFixed = 3 };      // beside kModeAppx / kModeV0 / kModeV1
 
 // LPR: lanes per value / lin_map row (Dp / 16); LPRK: lanes per key row (key_row_bytes / 16)
-template <int LPR, int LPRK, int MODE, int NB>
+// TOP: the attended slots of every hop besides (hops_attended_story.h::story_select_wave)
+template <int LPR, int LPRK, int MODE, int NB, bool TOP = false>
 __global__ void __launch_bounds__(kWave)
-k_hops_small(const HopArgs a, const uint32_t key_row_bytes)
+k_hops_small(const HopArgs a, const uint32_t key_row_bytes, const StoryTop<TOP> tp)
 {
     constexpr uint32_t Dp = LPR * 16, RPWK = kWave / LPRK;
     // bAbI width (Dp = 64): everything a hop reads from global memory -- its value rows, its linear-map
@@ -177,6 +179,7 @@ k_hops_small(const HopArgs a, const uint32_t key_row_bytes)
             if (a.tap_scores) a.tap_scores[tb] = (float)code * unit;
             if (a.tap_probs) a.tap_probs[tb] = p;
         }
+        if constexpr (TOP) story_select_wave(tp, (size_t)q * a.n_hop + h, S, p, lane);
 
         // read-out over the rows whose weight code is non-zero (the others add exact zeros)
         const uint64_t survivors = __ballot(kp != 0);

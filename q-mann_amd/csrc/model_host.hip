@@ -331,11 +331,14 @@ int ensure_float_matrices(qmann_model *m, void *stream)
 
 // hops + answer on the memories sitting in the workspace (hop planes rows_total . Dp apart; one shared plane when tied).
 // `split_ws`: the batch's index lists where with_side_branch below has made them, else null.
+// `top`: the attended slots of qmann_model_forward_words_top (rt.h::QmHopHints' top fields), or null.
 int hops_and_answer(qmann_model *m, uint32_t rows_total, const uint32_t *row_off, uint32_t max_slots, uint32_t n_query,
-                    const uint32_t *answer, uint32_t *pred, float *cost, uint32_t *match, void *stream, uint32_t *split_ws)
+                    const uint32_t *answer, uint32_t *pred, float *cost, uint32_t *match, void *stream, uint32_t *split_ws,
+                    const QmHopHints *top = nullptr)
 {
     const size_t hop_stride = m->tied ? 0 : (size_t)rows_total * m->Dp;
-    const QmHopHints hints{rows_total, split_ws};    // (a tied model passes hop_stride = 0: the hop kernels still learn the plane's size)
+    QmHopHints hints{rows_total, split_ws};          // (a tied model passes hop_stride = 0: the hop kernels still learn the plane's size)
+    if (top) { hints.top_on = true; hints.top_k = top->top_k; hints.top_slot = top->top_slot; hints.top_p = top->top_p; }
     int rc;
     if (use_planes(m, max_slots)) {
         const size_t key_hop_stride = m->tied ? 0 : (size_t)rows_total * (m->Dp / 64) * m->net.num_bit * 8;
@@ -359,7 +362,7 @@ int hops_and_answer(qmann_model *m, uint32_t rows_total, const uint32_t *row_off
 // row_off alone; 12 us of memset + kernel + launch gaps off the caller's stream): *split_ws, null where there are none.
 template <typename Story, typename Question>
 int with_side_branch(const qmann_model *m, uint32_t rows_total, const uint32_t *row_off, uint32_t max_slots, uint32_t n_query, void *stream,
-                     uint32_t **split_ws, Story &&story, Question &&question)
+                     uint32_t **split_ws, Story &&story, Question &&question, bool may_split = true)
 {
     hipStream_t st = (hipStream_t)stream;
     QmSide *sd = (n_query >= kQmCorunMinQueries && !qm_tuning().no_corun) ? qm_side_stream(st) : nullptr;
@@ -370,7 +373,7 @@ int with_side_branch(const qmann_model *m, uint32_t rows_total, const uint32_t *
     const int rc = story(stream);
     const int rc_q = question(sd ? (void *)sd->side : stream);
     *split_ws = nullptr;
-    if (sd && !rc_q && !use_planes(m, max_slots) && qm_hops_will_split(&m->net, rows_total, max_slots, n_query))
+    if (sd && !rc_q && may_split && !use_planes(m, max_slots) && qm_hops_will_split(&m->net, rows_total, max_slots, n_query))
         *split_ws = qm_split_early(row_off, n_query, max_slots, st, sd->side);
     if (sd) {                                            // (joined on every path: a capture must not end with an open branch)
         QM_HIP(hipEventRecord(sd->join, sd->side));
@@ -534,28 +537,57 @@ int qmann_model_net(const qmann_model *m, qmann_net *net, const float **w_ans)
     return QMANN_OK;
 }
 
-int qmann_model_forward_words(qmann_model *m, const uint16_t *story_words, uint32_t rows_total, uint32_t max_words,
+// qmann_model_forward_words (top null) and qmann_model_forward_words_top (the top fields of `top` as the caller gave them)
+static int forward_words_impl(qmann_model *m, const uint16_t *story_words, uint32_t rows_total, uint32_t max_words,
                               const uint16_t *question_words, uint32_t max_q_words, const uint32_t *row_off,
                               uint32_t max_slots, uint32_t n_query, const uint32_t *answer, uint32_t *pred,
-                              float *cost, uint32_t *match, void *stream)
+                              float *cost, uint32_t *match, void *stream, const QmHopHints *top)
 {
     QmBatched qm_scope;
     if (!m) return QMANN_EINVAL;
     if (n_query == 0) return QMANN_OK;                  // (an empty batch needs no arrays)
     m->last_n_query = 0;                                // (set again where this call succeeds)
     if ((!story_words && rows_total) || !question_words || !row_off || !pred) return QMANN_EINVAL;   // (every story may be empty)
+    if (top) {
+        // what qmann_hops_top_i8 would refuse behind its base call, said here ahead of any launch: the modes and lengths it does
+        // not serve, then its own arguments.  (Beyond 64 slots only fixed-point models pass: the packed-plane route is never taken.)
+        const uint32_t am = m->net.attention_mode;
+        if (am == QMANN_ATT_FLOAT || (am != QMANN_ATT_FIXED && max_slots > 64)) return QMANN_EUNSUPPORTED;
+        if (top->top_k < 1 || top->top_k > (uint32_t)QMANN_MAX_TOP_SLOTS || !top->top_slot || !top->top_p) return QMANN_EINVAL;
+    }
     DeviceScope on(m->device);
     int rc = ensure(m, rows_total, n_query, use_planes(m, max_slots));
     if (rc) return rc;
     uint32_t *split_ws;
     rc = with_side_branch(m, rows_total, row_off, max_slots, n_query, stream, &split_ws,
         [&](void *s) { return qmann_embed_story_idx(&m->emb_net, story_words, rows_total, max_words, 1, m->t_a, m->t_c, m->keys, m->vals, (size_t)rows_total * m->Dp, s); },
-        [&](void *s) { return qmann_embed_query_idx(&m->net, question_words, max_q_words, m->t_q, m->u0, n_query, s); });
+        [&](void *s) { return qmann_embed_query_idx(&m->net, question_words, max_q_words, m->t_q, m->u0, n_query, s); },
+        !top);                                              // (the top call's hop launch is never split by story length)
     if (rc) return rc;
-    rc = hops_and_answer(m, rows_total, row_off, max_slots, n_query, answer, pred, cost, match, stream, split_ws);
+    rc = hops_and_answer(m, rows_total, row_off, max_slots, n_query, answer, pred, cost, match, stream, split_ws, top);
     if (!rc) rc = qm_scope.rc();
     if (!rc) m->last_n_query = n_query;
     return rc;
+}
+
+int qmann_model_forward_words(qmann_model *m, const uint16_t *story_words, uint32_t rows_total, uint32_t max_words,
+                              const uint16_t *question_words, uint32_t max_q_words, const uint32_t *row_off,
+                              uint32_t max_slots, uint32_t n_query, const uint32_t *answer, uint32_t *pred,
+                              float *cost, uint32_t *match, void *stream)
+{
+    return forward_words_impl(m, story_words, rows_total, max_words, question_words, max_q_words, row_off, max_slots, n_query,
+                              answer, pred, cost, match, stream, nullptr);
+}
+
+int qmann_model_forward_words_top(qmann_model *m, const uint16_t *story_words, uint32_t rows_total, uint32_t max_words,
+                                  const uint16_t *question_words, uint32_t max_q_words, const uint32_t *row_off,
+                                  uint32_t max_slots, uint32_t n_query, const uint32_t *answer, uint32_t *pred,
+                                  float *cost, uint32_t *match, uint32_t k, uint32_t *top_slot, float *top_p, void *stream)
+{
+    QmHopHints top;
+    top.top_on = true; top.top_k = k; top.top_slot = top_slot; top.top_p = top_p;
+    return forward_words_impl(m, story_words, rows_total, max_words, question_words, max_q_words, row_off, max_slots, n_query,
+                              answer, pred, cost, match, stream, &top);
 }
 
 int qmann_model_forward_shared_words(qmann_model *m, const uint16_t *story_words, uint32_t n_rows, uint32_t max_words,

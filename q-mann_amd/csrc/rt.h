@@ -106,6 +106,12 @@ struct QmHopHints {
     size_t plane_rows = 0;
     // The index lists of THIS call's (row_off, n_query, max_slots) from qm_split_early, made ahead of the launch; null = none
     uint32_t *split_ws = nullptr;
+    // qmann_hops_top_i8: the call also returns each hop's attended slots -- top_slot / top_p [n_query][n_hop][top_k], unchecked
+    // until the base call's own refusals are through (the entry points check them last); top_on = false: a plain call
+    bool top_on = false;
+    uint32_t top_k = 0;
+    uint32_t *top_slot = nullptr;
+    float *top_p = nullptr;
 };
 // qmann_hops_i8 / qmann_hops_packed (include/qmann_batch.h) with the caller's hints         (batch_hops.hip, batch_hops_ham.hip)
 int qm_hops_i8(const qmann_net *net, const int8_t *keys, const int8_t *vals, size_t hop_stride, const uint32_t *row_off, uint32_t max_slots,
