@@ -32,15 +32,12 @@
 //      scans, the workgroup also sums e^(x_r - Xb) over the rows retired so far, Xb the largest score the attention format
 //      can hold.  Once that sum passes 2^frac (1 + 2^-6) every read-out weight of the hop is known to quantise to code 0
 //      whatever the unread rows hold (derivation: ScanStop below): the wavefronts leave the scan, steps 2 and 3 are skipped
-//      and the hop continues with o = 0, the result the full scan would have produced.
+//      and the hop continues with o = 0, the result the full scan would have produced.  Every wavefront posts its sum and
+//      looks at the workgroup's after each tile, in front of asking for another.
 #include "hops_mid.h"
 #include "hops_host.h"
 
 namespace {
-
-// Tiles a wavefront retires between two looks at the workgroup's running sum (even; another value: tools/build_variant.sh)
-constexpr uint32_t kStopCadence = 4;
-static_assert(kStopCadence >= 2 && kStopCadence % 2 == 0, "scan_rows asks its hook every two tiles");
 
 // Why a hop's key scan may end early.  The e^x softmax gives slot r the weight p_r = (float)(e_r / total), e_r =
 // expf(x_r - xmax) <= 1 and total = sum_r e_r in double (hops_common.h::sm_quot).  qm_code (qfmt.h) truncates p . 2^frac toward
@@ -54,30 +51,60 @@ static_assert(kStopCadence >= 2 && kStopCadence % 2 == 0, "scan_rows asks its ho
 // an exponent folded into one FMA (argument off by < 2e-5): the threshold 2^frac (1 + 2^-6) leaves 1.5 %, some twenty times
 // those errors together, and puts 1 / total far enough below 2^-frac that the float quotient cannot round up to it.  A NaN or
 // infinite scale makes the sum NaN, which never compares >= thr: such a hop runs the full path.
-// Each wavefront adds its lanes' sums to one LDS float every kStopCadence tiles (a returning LDS add: it sees the workgroup's
-// sum so far) and leaves when that has passed thr.  The sum only grows, so the other wavefronts follow within one cadence, and
-// the workgroup's decision behind the scan's barrier -- the same LDS word, read by all -- is "zero" whenever any wavefront left.
+// Posting and looking are two things (hops_common.h::scan_rows calls both once per tile).  post(): the lanes' sums meet in lane
+// 63 through six DPP steps (four v_add_f32_dpp within the rows of 16 lanes, two row broadcasts of a v_mov_b32_dpp and a
+// v_add_f32 each) and that lane adds them to one LDS float (ds_add_f32: nothing returned, nothing waited for).  peek(): a plain
+// LDS read of that word, issued when the tile's row sums are there; post() compares what it returned, behind the tile's
+// retiring, so that the read's latency hides under that arithmetic.  In all -- the masking of the one lane, the read, its wait
+// and the comparison included -- some 20 instructions per tile beside the 150 of the tile's arithmetic.
+// What a look sees is every wavefront's posts up to a tile ago -- a sum over retired rows like any other, only over fewer.  The
+// sum only grows, so the other wavefronts follow within a tile of their own, and the workgroup's decision behind the scan's
+// barrier -- the same LDS word, read by all -- is "zero" whenever any wavefront left.
 struct ScanStop {
-    float &lane_sum;          // this lane's e^(x_r - Xb) since the last flush (the retire hook adds to it)
+    typedef __attribute__((address_space(3))) float lds_float;
+    float &lane_sum;          // this lane's e^(x_r - Xb) since the last post (the retire hook adds to it)
     float *word;              // the workgroup's sum (LDS)
     float thr;
-    uint32_t lane, n;
-    // the lanes' sums into the workgroup's; every lane returns the workgroup's sum including them
-    __device__ __forceinline__ float flush()
+    uint32_t lane;
+    template <int CTRL, int ROWS, bool BOUND>
+    static __device__ __forceinline__ float dpp_addf(float v)
+    {
+        return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, ROWS, 0xF, BOUND));
+    }
+    // `seen`: what peek() returned for this tile.  The add is written out: as an atomicAdd the compiler wraps it in its loop
+    // over the active lanes, for the one lane there is.  The compiler's wait counting cannot see this instruction.  Inside the
+    // scan that is harmless: LDS operations complete in order, so one more of them in flight only makes a counted wait stricter,
+    // and nothing there reads the word but peek(), which may see any earlier state.  INVARIANT: every way from scan_rows to the
+    // barrier behind the scan, or to any other read of the word, goes through flush(), which waits for the add by hand -- the
+    // kernel calls it on its one path between the scan and that barrier, whichever way a wavefront left the scan.
+    // (The comparison stands in front of the add, so that its wait is for the read alone.)
+    __device__ __forceinline__ bool post(float seen)
     {
         float v = lane_sum;
         lane_sum = 0.0f;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-        float tot = 0.0f;
-        if (lane == 0) tot = atomicAdd(word, v) + v;
-        return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, tot)));
+        v = dpp_addf<0xB1, 0xF, true>(v);            // quad_perm [1,0,3,2]
+        v = dpp_addf<0x4E, 0xF, true>(v);            // quad_perm [2,3,0,1]
+        v = dpp_addf<0x141, 0xF, true>(v);           // row_half_mirror
+        v = dpp_addf<0x140, 0xF, true>(v);           // row_mirror: every lane holds its row's sum
+        v = dpp_addf<0x142, 0xA, false>(v);          // row_bcast:15 into rows 1 and 3 (the others add 0)
+        v = dpp_addf<0x143, 0xC, false>(v);          // row_bcast:31 into rows 2 and 3: lane 63 holds the wavefront's sum
+        const bool leave = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, seen))) >= thr;
+        const uint32_t at = (uint32_t)(__UINTPTR_TYPE__)(lds_float *)word;
+        if (lane == 63u) asm volatile("ds_add_f32 %0, %1" : : "v"(at), "v"(v) : "memory");
+        return leave;
     }
-    __device__ __forceinline__ bool operator()()
+    // what the lanes still hold, behind the scan
+    __device__ __forceinline__ void flush()
     {
-        if (++n < kStopCadence / 2) return false;
-        n = 0;
-        return flush() >= thr;
+        (void)post(0.0f);
+        asm volatile("s_waitcnt lgkmcnt(0)" : : : "memory");
+    }
+    // `dep`: a value the read has to wait for (no instruction: the index is 0, but the compiler cannot know it)
+    __device__ __forceinline__ float peek(int dep) const
+    {
+        uint32_t i = 0;
+        asm("; ScanStop::peek behind %1" : "+v"(i) : "v"(dep));
+        return ((const volatile lds_float *)(lds_float *)word)[i];
     }
 };
 
@@ -157,13 +184,14 @@ k_hops_fixed(const HopArgs a, const StoryTop<TOP> tp)
                 if constexpr (STOP) stop_sum += __builtin_amdgcn_exp2f(__builtin_fmaf((float)code, stop_k1, stop_k0));
             };
             if (S < (kWave / LPR) * kUnroll) scan_rows_short<LPR>(kb, S, row_sum, retire, lane, wave, nwaves);
-            else if (nwaves == kWaves) {
-                if constexpr (STOP) scan_rows<LPR, kUnroll, NT, kWaves>(kb, S, row_sum, retire, lane, wave, ScanStop{stop_sum, stop_word, stop_thr, lane, 0u});
+            else if (STOP || nwaves == kWaves) {        // (a stopping launch always has four wavefronts)
+                if constexpr (STOP) scan_rows<LPR, kUnroll, NT, kWaves>(kb, S, row_sum, retire, lane, wave, ScanStop{stop_sum, stop_word, stop_thr, lane});
                 else scan_rows<LPR, kUnroll, NT, kWaves>(kb, S, row_sum, retire, lane, wave);
             }
             else scan_rows<LPR, kUnroll, NT, 1>(kb, S, row_sum, retire, lane, wave);
-            // what the lanes still hold: the decision below is taken on the whole sum, whether or not a wavefront left early
-            if constexpr (STOP) (void)ScanStop{stop_sum, stop_word, stop_thr, lane, 0u}.flush();
+            // what the lanes still hold (the short scan posts nothing), and the wait for every post (ScanStop's invariant): the
+            // decision below is taken on the whole sum
+            if constexpr (STOP) ScanStop{stop_sum, stop_word, stop_thr, lane}.flush();
         }
         __syncthreads();
         // every weight code of this hop is 0 (ScanStop above): no softmax, no survivors, o = 0.  All threads read the one word.

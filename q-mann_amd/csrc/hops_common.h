@@ -269,8 +269,11 @@ struct ScanNoStop {};
 // One wavefront streams tiles of UN x (64 / LPR) rows; loads of the next tile are issued before
 // the current one is reduced (addresses are clamped to the last row instead of being predicated,
 // so the loop body has no divergent control flow and the compiler can count its vmcnt waits).
-// `stop`: asked once per loop iteration (two tiles retired); a wavefront-uniform true ends this wavefront's scan -- the tile
-// already requested is dropped (its addresses were in range like every other tile's).  The hook keeps its own cadence.
+// `stop` (any type but ScanNoStop; the loop is then the second one below, same tiles in the same order): once a tile's row sums
+// are complete the wavefront calls stop.peek(dep) -- `dep` one of those sums, so that the hook can tie its read behind the
+// tile's arrival --, retires the tile, hands what peek returned to stop.post(), and leaves if that says so (wavefront-uniform),
+// BEFORE it asks for the tile after next: the one tile then in flight is dropped (its addresses were in range like every
+// other tile's).
 template <int LPR, int UN, bool NT, int NW, typename RowSum, typename Retire, typename Stop = ScanNoStop>
 __device__ __forceinline__ void scan_rows(const uint8_t *__restrict__ kb, uint32_t S, RowSum row_sum, Retire retire,
                                           uint32_t lane, uint32_t wave, Stop stop = Stop{})
@@ -315,6 +318,37 @@ __device__ __forceinline__ void scan_rows(const uint8_t *__restrict__ kb, uint32
     uint32_t base = wave * TILE;
     constexpr uint32_t STEP = nwaves * TILE;
     issue(xa, base);
+    if constexpr (!std::is_same<Stop, ScanNoStop>::value) {
+        // the loop below turned by half a step, so that a wavefront decides between retiring a tile and asking for the next but
+        // one; a tile behind the last is asked for like the others (its start is moved back into range) and never retired.
+        // step: `reduce` with the hook's two calls in it
+        auto step = [&](const i32x4 (&x)[UN], uint32_t at) {
+            int s[UN];
+#pragma unroll
+            for (int j = 0; j < UN; j++) s[j] = row_lanes_sum<LPR>(row_sum(x[j]));
+            const auto seen = stop.peek(s[UN - 1]);
+            const uint32_t start = tile_start(at);
+#pragma unroll
+            for (int j0 = 0; j0 < UN; j0 += LPR) {
+                int v = s[j0];
+#pragma unroll
+                for (int t = 1; t < LPR && j0 + t < UN; t++) v = (chunk == (uint32_t)t) ? s[j0 + t] : v;
+                const uint32_t j = j0 + chunk;
+                const uint32_t r = start + j * RPW + sub;
+                if (j < (uint32_t)UN && r >= at) retire(r, v);
+            }
+            return stop.post(seen);
+        };
+        issue(xb, base + STEP);
+        for (uint32_t t = wave;;) {
+            if (step(xa, base) || (t += nwaves) >= n_tiles) break;
+            issue(xa, base + 2 * STEP);
+            if (step(xb, base + STEP) || (t += nwaves) >= n_tiles) break;
+            issue(xb, base + 3 * STEP);
+            base += 2 * STEP;
+        }
+        return;
+    }
     for (uint32_t t = wave; t < n_tiles; t += 2 * nwaves) {
         issue(xb, base + STEP);
         reduce(xa, base);
@@ -322,8 +356,6 @@ __device__ __forceinline__ void scan_rows(const uint8_t *__restrict__ kb, uint32
         issue(xa, base + 2 * STEP);
         reduce(xb, base + STEP);
         base += 2 * STEP;
-        if constexpr (!std::is_same<Stop, ScanNoStop>::value)
-            if (stop()) break;
     }
 }
 
