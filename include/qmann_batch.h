@@ -355,7 +355,7 @@ int qmann_answer_f32_serial(const qmann_net *net, const float *w_ans, const floa
  * equal probabilities: higher index first" -- the tie rule of pred (lib/layer_cuda.cu:1918-1939), so top_idx[q][0] is the serial
  * call's pred[q] always, also among probabilities that underflowed to 0.  Every softmax base.  The kernels are the serial-order
  * ones of the shape with k rounds of their arg-max reduction behind the quotients (csrc/batch_answer.hip); the fused bf16 form
- * has no ranked build, and there is none for qmann_answer_i8's int8 matrices: a host of those ranks dequantised weights here.
+ * has no ranked build; qmann_answer_i8's int8 matrices have one of their own, qmann_answer_topk_i8 below.
  * One ordered step on `stream`, no allocation, no library scratch, no second stream: it can be captured in a graph.
  * Nothing is launched and the code returned is: QMANN_EINVAL for null pointers, k = 0, k > QMANN_MAX_TOPK, k > dim_input,
  * dim_emb = 0, dim_input = 0; QMANN_ERANGE where qmann_answer_f32_serial answers it (a query's LDS beyond 128 KiB, 2^24 queries
@@ -385,6 +385,42 @@ int qmann_answer_topk_f32(const qmann_net *net, const float *w_ans, const float 
 int qmann_answer_i8(const qmann_net *net, const int8_t *w_ans_i8, qmann_fmt w_fmt, const float *u,
                     float *logits_ws, const uint32_t *answer, uint32_t *pred, float *probs, float *cost,
                     uint32_t *match, uint32_t n_query, void *stream);
+
+/* Ranked answers for the int8 answer layer: per query the k answers with the largest logits and their probabilities, projection,
+ * softmax statistics and selection in ONE pass on the int8 matrix cores -- no [n_query][V] array in that form.
+ *   net, w_ans_i8 [V][Dp], w_fmt, u: exactly qmann_answer_i8's operands (u is read through the last hop's activation format:
+ *       truncation toward zero, symmetric saturation, so off-grid and saturating u behave as they do there).
+ *   top_idx [n_query][k] uint32, top_p [n_query][k] float; 1 <= k <= QMANN_MAX_TOPK, k <= dim_input.
+ * Ranking.  K[q][v] is the integer logit code, query codes times row v of w_ans_i8 -- the integer the matrix cores produce.  Row q
+ * of top_idx lists the k answers that come first in the order "larger K first, equal K: higher index first"; top_idx[q][0] is
+ * qmann_answer_i8's pred[q] always.  The order is exact by construction: a candidate is the 64-bit key ((K + 2^28) << 32) | v.
+ * This differs from qmann_answer_topk_f32 ON PURPOSE: that call ranks the ROUNDED PROBABILITIES, so two different logits whose
+ * probabilities round to the same float (denormals or 0, once the exponential underflows) are ordered by index there; here they
+ * stay ordered by logit.  Wherever the listed probabilities are pairwise distinct or the codes are equal the two orders coincide.
+ * Probabilities.
+ *   One-pass form: top_p[q][j] = e^((K - max) . scale) / total (or the 2^x base's), with the running-maximum normaliser of
+ *       qmann_answer_i8's one-pass form: within rtol 1e-5 / atol 1e-7 of the float64 softmax of the exact logits.
+ *   Two-kernel form -- taken exactly where qmann_answer_i8 takes it whatever `probs` is: the exp_plan base, QMANN_ANSWER_TWO_PASS,
+ *       a dictionary of 1, 2 or 3 answers: logits to the workspace, then the float path's softmax on them; top_p[q][j] is BIT-EQUAL
+ *       to probs[q][top_idx[q][j]] of qmann_answer_i8(..., probs != NULL) on the same inputs.  The order is still the logit order.
+ * ws: the caller's workspace, 8-byte aligned, at least qmann_answer_topk_i8_ws_bytes(net, k, n_query) bytes: the larger of the
+ * two-kernel form's float [n_query][V] (rounded up to 8 bytes) and the one-pass records -- per dictionary slice and query 16 bytes
+ * (maximum, sum) plus k keys of 8 bytes, the slices being those of qmann_answer_i8 for the same batch (at most ceil(V / 64)).  The
+ * figure does not depend on the form, so a switch flipped between the two calls does no harm.  The helper answers 0 for a net or k
+ * the call would refuse.  The contents need not survive between calls.
+ * One ordered step on `stream` (two kernels), no allocation, no library scratch, no second stream: it can be captured in a graph.
+ * Nothing is launched, no output is touched and the code returned is, in this order, the first that applies:
+ *   1. every refusal of qmann_answer_i8 for net, w_ans_i8, w_fmt, u, the dimensions, the formats and a query's LDS, with its codes
+ *      (top_idx / top_p take pred's place in the null check);
+ *   2. QMANN_EINVAL for k = 0, k > QMANN_MAX_TOPK or k > dim_input;
+ *   3. QMANN_EINVAL for a null or misaligned ws, or ws_bytes below the helper's figure for this call;
+ *   4. QMANN_OK for n_query = 0;
+ *   5. QMANN_ERANGE for 2^24 queries or more;
+ *   6. QMANN_EUNSUPPORTED for a dim_emb_pad other than 64, 128 or 256. */
+size_t qmann_answer_topk_i8_ws_bytes(const qmann_net *net, uint32_t k, uint32_t n_query);
+int qmann_answer_topk_i8(const qmann_net *net, const int8_t *w_ans_i8, qmann_fmt w_fmt, const float *u,
+                         void *ws, size_t ws_bytes, uint32_t k, uint32_t *top_idx, float *top_p,
+                         uint32_t n_query, void *stream);
 
 /* Story / question embedding for a batch of bag-of-words inputs (dense_mat_fwd / dense_fwd,
  * lib/layer_cuda.cu:3511, :3162), writing the int8 memories directly.

@@ -193,6 +193,8 @@ _proto("qmann_answer_f32", C.c_int, [C.POINTER(Net), _vp, _vp, _vp, _vp, _vp, _v
 _proto("qmann_answer_f32_serial", C.c_int, [C.POINTER(Net), _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, _vp])
 _proto("qmann_answer_topk_f32", C.c_int, [C.POINTER(Net), _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp])
 _proto("qmann_answer_i8", C.c_int, [C.POINTER(Net), _vp, Fmt, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, _vp])
+_proto("qmann_answer_topk_i8_ws_bytes", C.c_size_t, [C.POINTER(Net), C.c_uint32, C.c_uint32])
+_proto("qmann_answer_topk_i8", C.c_int, [C.POINTER(Net), _vp, Fmt, _vp, _vp, C.c_size_t, C.c_uint32, _vp, _vp, C.c_uint32, _vp])
 _proto("qmann_embed_story", C.c_int, [C.POINTER(Net), _vp, C.c_uint32, C.POINTER(_vp), C.POINTER(_vp), _vp, _vp,
                                       C.c_size_t, _vp])
 _proto("qmann_quantize_table_i8", C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, Fmt, _vp])

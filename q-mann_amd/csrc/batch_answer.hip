@@ -19,6 +19,10 @@ namespace {
 // probabilities are the ones the statements below leave in LDS, so they are the serial layer's bit for bit; k rounds of the
 // arg-max reduction, a taken entry marked by a negative value (probabilities are >= 0).  k <= V: every round finds an untaken one.
 // The ranked builds are instantiations of their own: the others take an EMPTY last argument and keep their device code.
+// PRECOMPUTED && TOPK (qmann_answer_topk_i8's two-kernel form): the probabilities are formed by the same statements, but the k
+// rounds rank by the LOGITS still in the buffer (float code . scale, exact: the order of the integer codes), ties to the higher
+// index; what is listed is the probability LDS holds for the winner.  Distinct codes whose probabilities round to one float stay
+// in logit order that way.
 template <bool TOPK> struct AnsTopK {};
 template <> struct AnsTopK<true> { uint32_t *idx; float *p; uint32_t k; };
 
@@ -103,6 +107,7 @@ k_answer(const float *__restrict__ w_ans, const float *__restrict__ u, const uin
         __syncthreads();                             // all wavefronts have read the terms before the quotients replace them
     }
 
+    constexpr bool BY_LOGIT = PRECOMPUTED && TOPK;
     float bv = -INFINITY;
     uint32_t bi = 0;
     for (uint32_t v = tid; v < V; v += kBlock) {
@@ -110,7 +115,12 @@ k_answer(const float *__restrict__ w_ans, const float *__restrict__ u, const uin
                                                             : lg[v] / (float)total;
         lg[v] = p;
         if (!TOPK && probs) probs[(size_t)q * V + v] = p;
-        if (!(bv > p)) { bv = p; bi = v; }           // later index wins a tie
+        if constexpr (BY_LOGIT) {
+            const float x = w_ans[(size_t)q * V + v];
+            if (!(bv > x)) { bv = x; bi = v; }
+        } else {
+            if (!(bv > p)) { bv = p; bi = v; }       // later index wins a tie
+        }
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
@@ -126,7 +136,7 @@ k_answer(const float *__restrict__ w_ans, const float *__restrict__ u, const uin
             if (red_f[i] > bv || (red_f[i] == bv && red_i[i] > bi)) { bv = red_f[i]; bi = red_i[i]; }
         if constexpr (TOPK) {
             tk.idx[(size_t)q * tk.k] = bi;
-            tk.p[(size_t)q * tk.k] = bv;
+            tk.p[(size_t)q * tk.k] = BY_LOGIT ? lg[bi] : bv;
             lg[bi] = -1.0f;
         } else {
             pred[q] = bi;
@@ -146,7 +156,12 @@ k_answer(const float *__restrict__ w_ans, const float *__restrict__ u, const uin
             bi = 0;
             for (uint32_t v = tid; v < V; v += kBlock) {
                 const float p = lg[v];
-                if (!(bv > p)) { bv = p; bi = v; }
+                if constexpr (BY_LOGIT) {
+                    const float x = w_ans[(size_t)q * V + v];
+                    if (p >= 0.0f && !(bv > x)) { bv = x; bi = v; }      // (k <= V: an untaken logit, all finite, is always left)
+                } else {
+                    if (!(bv > p)) { bv = p; bi = v; }
+                }
             }
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) {
@@ -160,7 +175,7 @@ k_answer(const float *__restrict__ w_ans, const float *__restrict__ u, const uin
                 for (int i = 1; i < kWaves; i++)
                     if (red_f[i] > bv || (red_f[i] == bv && red_i[i] > bi)) { bv = red_f[i]; bi = red_i[i]; }
                 tk.idx[(size_t)q * tk.k + j] = bi;
-                tk.p[(size_t)q * tk.k + j] = bv;
+                tk.p[(size_t)q * tk.k + j] = BY_LOGIT ? lg[bi] : bv;
                 lg[bi] = -1.0f;
             }
         }
@@ -644,10 +659,61 @@ __device__ __forceinline__ float ans_term(int dk, float scale, float scale_log2e
     return sm_exp((float)dk * scale, c);
 }
 
-template <int KSTEPS, bool EXPB>
+// ---- ranked builds (qmann_answer_topk_i8) ------------------------------------------------------------------------------------------
+// A candidate is the 64-bit key ((code + 2^28) << 32) | index: "larger key first" is the whole order -- larger code first, equal
+// codes: higher index first -- and 0 is below every candidate (no code is as low as kAnsFloor).
+// The 16 lanes that share a group of 4 query rows (equal lane >> 4: one DPP row) hold each row's sorted list DISTRIBUTED: lane c
+// holds entry c, 4 keys = 8 registers per lane at any k <= 16.  Entries beyond k - 1 are kept too (they cost nothing), the bar
+// a candidate must pass is entry k - 1.
+__device__ __forceinline__ uint64_t ans_key(int code, uint32_t v)
+{
+    return ((uint64_t)(uint32_t)(code - kAnsFloor) << 32) | v;
+}
+// the left neighbour's entry within the DPP row (row_shr:1); lane 0 of a row reads "above everything"
+__device__ __forceinline__ uint64_t ans_left_entry(uint64_t e)
+{
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)(uint32_t)e, 0x111, 0xF, 0xF, false);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)(uint32_t)(e >> 32), 0x111, 0xF, 0xF, false);
+    return (uint64_t)lo | ((uint64_t)hi << 32);
+}
+// Every lane brings N candidates `key` for the list `e` of its lane group (0: none).  Those above the group's k-th entry are
+// inserted one at a time: a lane offers its best one, a lane is picked from the group's 16 ballot bits, its key broadcast within
+// the group, and every lane shifts or keeps its entry.  The four lane groups insert in parallel; the trip count is wavefront-
+// uniform (the ballot): one trip per insertion of the busiest group, and one shuffle for the bar that each insertion raises.
+template <int N>
+__device__ __forceinline__ void ans_list_insert(uint64_t &e, uint64_t (&key)[N], uint32_t lane, uint32_t k)
+{
+    const uint32_t base = lane & 48u;
+    uint64_t bar = __shfl(e, (int)(base + k - 1));
+    for (;;) {
+        uint64_t m = key[0];
+#pragma unroll
+        for (int i = 1; i < N; i++) m = key[i] > m ? key[i] : m;
+        const uint64_t bal = __ballot(m > bar);
+        if (bal == 0) break;                                         // (wavefront-uniform)
+        const uint32_t bits = (uint32_t)(bal >> base) & 0xFFFFu;
+        const uint32_t src = bits ? base + (uint32_t)__builtin_ctz(bits) : lane;
+        uint64_t c = __shfl(m, (int)src);
+        c = bits ? c : 0;                                            // a group with nothing pending keeps its list
+        if (bits && src == lane) {
+#pragma unroll
+            for (int i = 0; i < N; i++) key[i] = key[i] == m ? 0 : key[i];      // (keys are distinct)
+        }
+        const uint64_t left = ans_left_entry(e);
+        e = c > e ? (left > c ? c : left) : e;                       // entries above c stay, c lands, the rest move right
+        bar = __shfl(e, (int)(base + k - 1));
+    }
+}
+
+template <bool TOPK> struct AnsTopKI8 {};
+template <> struct AnsTopKI8<true> { uint64_t *keys; uint32_t k; };    // keys [n_slice][n_query][k]: a slice's list per query, best first, 0 = empty
+
+// TOPK: the ranked build also keeps the k best keys of the slice per query and writes them to tk.keys; max and sum as ever.
+template <int KSTEPS, bool EXPB, bool TOPK = false>
 __global__ void __launch_bounds__(kBlock)
 k_answer_i8_part(const float *__restrict__ u, const int8_t *__restrict__ w, AnsPart *__restrict__ part,
-                 uint32_t n_query, uint32_t D, uint32_t V, QFmt fu, float scale, uint32_t softmax_base, uint32_t tiles_per_slice)
+                 uint32_t n_query, uint32_t D, uint32_t V, QFmt fu, float scale, uint32_t softmax_base, uint32_t tiles_per_slice,
+                 const AnsTopKI8<TOPK> tk)
 {
     constexpr uint32_t Dp = KSTEPS * 64, PITCH = Dp + 16, NB = kAnsTile / 16;
     __shared__ __attribute__((aligned(16))) uint8_t tile[2][kAnsTile * PITCH];
@@ -690,6 +756,7 @@ k_answer_i8_part(const float *__restrict__ u, const int8_t *__restrict__ w, AnsP
     int mx[4] = {kAnsFloor, kAnsFloor, kAnsFloor, kAnsFloor};       // (no logit is that low: the first one becomes the maximum)
     uint32_t bi[4] = {0, 0, 0, 0};
     double sm[4] = {0.0, 0.0, 0.0, 0.0};
+    uint64_t lst[TOPK ? 4 : 1] = {};                                 // (ranked build) entry `row` of the sorted lists of query rows 4 kq + r
 
     const uint32_t n_tiles = (V + kAnsTile - 1) / kAnsTile;
     const uint32_t t_lo = blockIdx.y * tiles_per_slice, t_hi = (t_lo + tiles_per_slice < n_tiles) ? t_lo + tiles_per_slice : n_tiles;
@@ -751,6 +818,23 @@ k_answer_i8_part(const float *__restrict__ u, const int8_t *__restrict__ w, AnsP
             sm[r] = sm[r] * (double)fs + (double)e;
             mx[r] = mn;
         }
+        if constexpr (TOPK) {
+            // this lane's 4 fresh codes of each row against the row's k-th entry: a row of queries is skipped where no lane of
+            // the wavefront brings one above it -- most rows, once the first tiles of the slice are through
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const uint64_t bar = __shfl(lst[r], (int)((lane & 48u) + tk.k - 1));
+                uint64_t fresh[NB];
+                bool any = false;
+#pragma unroll
+                for (uint32_t nb = 0; nb < NB; nb++) {
+                    const uint64_t key = v0 + 16 * nb < V ? ans_key(acc[nb][r], v0 + 16 * nb) : 0;
+                    fresh[nb] = key > bar ? key : 0;
+                    any |= key > bar;
+                }
+                if (__ballot(any)) ans_list_insert<NB>(lst[r], fresh, lane, tk.k);     // (wavefront-uniform)
+            }
+        }
         if (t + 1 < t_hi) put(b ^ 1u);
         __syncthreads();
     }
@@ -775,6 +859,53 @@ k_answer_i8_part(const float *__restrict__ u, const int8_t *__restrict__ w, AnsP
         for (int r = 0; r < 4; r++) {
             const uint32_t q = m0 + 4 * kq + r;
             if (q < n_query) part[(size_t)blockIdx.y * n_query + q] = AnsPart{mx[r], bi[r], sm[r]};
+        }
+    }
+    if constexpr (TOPK) {                                                // the lists are merged across the lanes already
+        if (row < tk.k) {
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const uint32_t q = m0 + 4 * kq + r;
+                if (q < n_query) tk.keys[((size_t)blockIdx.y * n_query + q) * tk.k + row] = lst[r];
+            }
+        }
+    }
+}
+
+// The ranked combine: 16 lanes per query merge the slices' lists into one distributed list (ans_list_insert again; a slice's
+// list is sorted, so its lanes stop passing the bar early), the maximum and the total merge as in k_answer_i8_combine, and lane j
+// writes pick j: its index and e^((code - max) . scale) / total, formed as that kernel forms the labelled answer's probability.
+__global__ void __launch_bounds__(kBlock)
+k_answer_i8_combine_topk(const AnsPart *__restrict__ part, const uint64_t *__restrict__ keys, uint32_t *__restrict__ top_idx,
+                         float *__restrict__ top_p, uint32_t n_query, uint32_t n_slice, uint32_t k, float scale, uint32_t softmax_base)
+{
+    const SmCfg smc{softmax_base, false, false, 1.0f};
+    const uint32_t lane = threadIdx.x & (kWave - 1), sub = lane & 15;
+    const uint32_t wave_g = (blockIdx.x * kBlock + threadIdx.x) / kWave, n_wave = gridDim.x * (kBlock / kWave);
+    for (uint32_t qb = wave_g * 4; qb < n_query; qb += n_wave * 4) {              // wavefront-uniform trip count
+        const uint32_t q = qb + (lane >> 4);
+        const bool q_ok = q < n_query;
+        uint64_t e = 0;
+        for (uint32_t s = 0; s < n_slice; s++) {
+            uint64_t key[1] = {(q_ok && sub < k) ? keys[((size_t)s * n_query + q) * k + sub] : 0};
+            ans_list_insert<1>(e, key, lane, k);
+        }
+        if (!q_ok) continue;
+        int M = kAnsFloor;
+        for (uint32_t s = 0; s < n_slice; s++) {
+            const int m = part[(size_t)s * n_query + q].m;
+            M = m > M ? m : M;
+        }
+        double total = 0.0;
+        for (uint32_t s = 0; s < n_slice; s++) {
+            const AnsPart p = part[(size_t)s * n_query + q];
+            total += p.sum * (p.m == M ? 1.0 : (double)sm_exp((float)(p.m - M) * scale, smc));
+        }
+        if (sub < k) {
+            const int code = (int)(uint32_t)(e >> 32) + kAnsFloor;
+            const float x = sm_exp((float)(code - M) * scale, smc);
+            top_idx[(size_t)q * k + sub] = (uint32_t)e;
+            top_p[(size_t)q * k + sub] = (softmax_base == QMANN_SOFTMAX_EXP) ? (float)((double)x / total) : x / (float)total;
         }
     }
 }
@@ -856,6 +987,45 @@ static AnsSmallPlan ans_small_plan(uint32_t D, uint32_t V)
     p.qpw = kWave / p.lpq * qb;
     p.lds = ((size_t)D * p.lpq * p.vpt + (size_t)kAnsWaves * p.qpw * D) * sizeof(float);
     p.fits = V <= 256u && p.lds <= 78 * 1024;
+    return p;
+}
+
+// the one-pass int8 form's grid: 64 queries per workgroup, the dictionary's 64-row tiles cut into slices
+struct AnsSlices { uint32_t qblocks, n_slice, tps; };
+static AnsSlices ans_i8_slices(uint32_t n_query, uint32_t V)
+{
+    const uint32_t qblocks = (n_query + 16 * kWaves - 1) / (16 * kWaves), n_tiles = (V + kAnsTile - 1) / kAnsTile;
+    // ~2 workgroups per CU (measured at 8 192 x 4 096 x 256: 128 workgroups 86 us, 256: 55, 512: 45, 1 024: 46)
+    uint32_t n_slice = qblocks >= 512u ? 1u : (512u + qblocks - 1) / qblocks;
+    if (n_slice > n_tiles) n_slice = n_tiles;
+    const uint32_t tps = (n_tiles + n_slice - 1) / n_slice;
+    return AnsSlices{qblocks, (n_tiles + tps - 1) / tps, tps};
+}
+
+// qmann_answer_i8's refusals that depend on the net and the matrix format alone (its codes, its order)
+static int answer_i8_net_check(const qmann_net *net, qmann_fmt w_fmt)
+{
+    const uint32_t D = net->dim_emb, Dp = net->dim_emb_pad, V = net->dim_input;
+    if (D == 0 || V == 0 || Dp % 64 != 0 || D > Dp) return QMANN_EINVAL;
+    if (!qm_fmt8(net->act[net->n_hop - 1]) || !qm_fmt8(w_fmt)) return QMANN_ERANGE;
+    if (((size_t)((D + 3) & ~3u) + V) * sizeof(float) > 128 * 1024) return QMANN_ERANGE;
+    return QMANN_OK;
+}
+
+// qmann_answer_topk_i8's form and workspace for (net, k, n_query): the two-kernel form exactly where qmann_answer_i8 takes it
+// whatever `probs` is; otherwise the slices of that call with records of 16 + 8 k bytes -- AnsPart [n_slice][n_query], then the
+// keys [n_slice][n_query][k].  The workspace covers both forms, so a switch flipped between the helper and the call changes nothing.
+struct AnsTopKI8Plan { bool one_pass; AnsSlices sl; size_t bytes; };
+static AnsTopKI8Plan answer_topk_i8_plan(const qmann_net *net, uint32_t k, uint32_t n_query)
+{
+    AnsTopKI8Plan p{false, AnsSlices{0, 0, 0}, 0};
+    if (n_query == 0) return p;
+    const uint32_t V = net->dim_input;
+    p.one_pass = net->softmax_base != QMANN_SOFTMAX_EXP_PLAN && !qm_tuning().answer_two_pass && (size_t)V * sizeof(float) >= sizeof(AnsPart);
+    p.sl = ans_i8_slices(n_query, V);
+    const size_t logits = ((size_t)n_query * V * sizeof(float) + 7) & ~(size_t)7;
+    const size_t records = (size_t)p.sl.n_slice * n_query * (sizeof(AnsPart) + (size_t)k * sizeof(uint64_t));
+    p.bytes = (V >= 4 && records > logits) ? records : logits;
     return p;
 }
 
@@ -969,20 +1139,17 @@ int qmann_answer_i8(const qmann_net *net, const int8_t *w_ans_i8, qmann_fmt w_fm
     const bool records_fit = (size_t)V * sizeof(float) >= sizeof(AnsPart);
     if (!probs && net->softmax_base != QMANN_SOFTMAX_EXP_PLAN && !qm_tuning().answer_two_pass && records_fit) {
         // one pass: no logits round trip; the workspace holds the per-slice records
-        const uint32_t qblocks = (n_query + 16 * kWaves - 1) / (16 * kWaves), n_tiles = (V + kAnsTile - 1) / kAnsTile;
-        // ~2 workgroups per CU (measured at 8 192 x 4 096 x 256: 128 workgroups 86 us, 256: 55, 512: 45, 1 024: 46)
-        uint32_t n_slice = qblocks >= 512u ? 1u : (512u + qblocks - 1) / qblocks;
-        if (n_slice > n_tiles) n_slice = n_tiles;
         // the records fit logits_ws: V >= 4 here, and n_slice <= ceil(V / 64) gives 16 n_slice <= 4 V bytes per query
-        const uint32_t tps = (n_tiles + n_slice - 1) / n_slice;
-        n_slice = (n_tiles + tps - 1) / tps;
+        const AnsSlices sl = ans_i8_slices(n_query, V);
+        const uint32_t qblocks = sl.qblocks, n_slice = sl.n_slice, tps = sl.tps;
         AnsPart *part = (AnsPart *)logits_ws;
         const dim3 grid1(qblocks, n_slice);
         const bool eb = net->softmax_base == QMANN_SOFTMAX_EXP;
         if (!qm_dispatch<64, 128, 256>(Dp, [&](auto dp) {
                 constexpr int KS = decltype(dp)::value / 64;
                 qm_dispatch<false, true>(eb, [&](auto e) {
-                    k_answer_i8_part<KS, decltype(e)::value><<<grid1, kBlock, 0, st>>>(u, w_ans_i8, part, n_query, D, V, fuq, scale, net->softmax_base, tps);
+                    k_answer_i8_part<KS, decltype(e)::value><<<grid1, kBlock, 0, st>>>(u, w_ans_i8, part, n_query, D, V, fuq, scale, net->softmax_base, tps,
+                                                                                       AnsTopKI8<false>{});
                 });
             }))
             return QMANN_EUNSUPPORTED;
@@ -1002,6 +1169,66 @@ int qmann_answer_i8(const qmann_net *net, const int8_t *w_ans_i8, qmann_fmt w_fm
     qm_launch(k_answer<true>, n_query < 8192u ? n_query : 8192u, kBlock, lds, st,
               logits_ws, nullptr, answer, pred, probs, cost, match, D, V, net->softmax_base, n_query,
               sp.fits ? sp.lpq : 0u, sp.lpq == 64u ? 4u : sp.vpt, AnsTopK<false>{});
+    QM_LAUNCH_CHECK();
+    return qm_scope.rc();
+}
+
+size_t qmann_answer_topk_i8_ws_bytes(const qmann_net *net, uint32_t k, uint32_t n_query)
+{
+    if (!net || net->n_hop == 0 || net->n_hop > QMANN_MAX_HOP) return 0;
+    const uint32_t D = net->dim_emb, Dp = net->dim_emb_pad, V = net->dim_input;
+    if (D == 0 || V == 0 || Dp % 64 != 0 || D > Dp || !qm_fmt8(net->act[net->n_hop - 1])) return 0;
+    if (((size_t)((D + 3) & ~3u) + V) * sizeof(float) > 128 * 1024) return 0;
+    if (k == 0 || k > QMANN_MAX_TOPK || k > V || (Dp != 64 && Dp != 128 && Dp != 256)) return 0;
+    return answer_topk_i8_plan(net, k, n_query).bytes;
+}
+
+int qmann_answer_topk_i8(const qmann_net *net, const int8_t *w_ans_i8, qmann_fmt w_fmt, const float *u, void *ws, size_t ws_bytes,
+                         uint32_t k, uint32_t *top_idx, float *top_p, uint32_t n_query, void *stream)
+{
+    if (!net || !w_ans_i8 || !u || !top_idx || !top_p) return QMANN_EINVAL;
+    if (const int rc = answer_i8_net_check(net, w_fmt)) return rc;
+    const uint32_t D = net->dim_emb, Dp = net->dim_emb_pad, V = net->dim_input;
+    if (k == 0 || k > QMANN_MAX_TOPK || k > V) return QMANN_EINVAL;
+    const AnsTopKI8Plan plan = answer_topk_i8_plan(net, k, n_query);
+    if (!ws || ((uintptr_t)ws & 7u) || ws_bytes < qmann_answer_topk_i8_ws_bytes(net, k, n_query)) return QMANN_EINVAL;
+    if (n_query == 0) return QMANN_OK;
+    if (qm_too_many_queries(n_query)) return QMANN_ERANGE;
+    if (Dp != 64 && Dp != 128 && Dp != 256) return QMANN_EUNSUPPORTED;
+    QmBatched qm_scope;
+    const qmann_fmt fu = net->act[net->n_hop - 1];
+    const float scale = 1.0f / (float)(1u << (fu.frac + w_fmt.frac));
+    hipStream_t st = (hipStream_t)stream;
+    const QFmt fuq = qm_qfmt(fu);
+    if (plan.one_pass) {
+        const AnsSlices sl = plan.sl;
+        AnsPart *part = (AnsPart *)ws;
+        const AnsTopKI8<true> tk{(uint64_t *)(part + (size_t)sl.n_slice * n_query), k};
+        const dim3 grid1(sl.qblocks, sl.n_slice);
+        const bool eb = net->softmax_base == QMANN_SOFTMAX_EXP;
+        qm_dispatch<64, 128, 256>(Dp, [&](auto dp) {
+            constexpr int KS = decltype(dp)::value / 64;
+            qm_dispatch<false, true>(eb, [&](auto e) {
+                k_answer_i8_part<KS, decltype(e)::value, true><<<grid1, kBlock, 0, st>>>(u, w_ans_i8, part, n_query, D, V, fuq, scale, net->softmax_base,
+                                                                                         sl.tps, tk);
+            });
+        });
+        const uint32_t cb = (n_query * 16 + kBlock - 1) / kBlock;
+        k_answer_i8_combine_topk<<<cb < 2048u ? cb : 2048u, kBlock, 0, st>>>(part, tk.keys, top_idx, top_p, n_query, sl.n_slice, k, scale, net->softmax_base);
+        QM_LAUNCH_CHECK();
+        return qm_scope.rc();
+    }
+    float *logits = (float *)ws;
+    const dim3 grid((n_query + 16 * kWaves - 1) / (16 * kWaves), (V + 16 * kTilesPerBlockY - 1) / (16 * kTilesPerBlockY));
+    qm_dispatch<64, 128, 256>(Dp, [&](auto dp) {
+        k_logits_mfma_i8<decltype(dp)::value / 64><<<grid, kBlock, 0, st>>>(u, w_ans_i8, logits, n_query, D, V, fuq, scale);
+    });
+    // k_answer<true>'s launch, in its ranked build: the same normaliser order, hence qmann_answer_i8's probabilities bit for bit
+    const AnsSmallPlan sp = ans_small_plan(D, V);
+    const size_t lds = ((size_t)((D + 3) & ~3u) + V) * sizeof(float);
+    qm_launch(k_answer<true, true>, n_query < 8192u ? n_query : 8192u, kBlock, lds, st,
+              logits, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, D, V, net->softmax_base, n_query,
+              sp.fits ? sp.lpq : 0u, sp.lpq == 64u ? 4u : sp.vpt, AnsTopK<true>{top_idx, top_p, k});
     QM_LAUNCH_CHECK();
     return qm_scope.rc();
 }

@@ -536,6 +536,20 @@ class QNet:
                                           self._s()), "qmann_answer_i8")
         return pred, probs, cost, match, logits
 
+    def answer_topk_i8(self, u, w_ans_i8, w_fmt, k):
+        """qmann_answer_topk_i8: per row of u the k answers with the largest integer logits of the int8 answer layer, (top_idx
+        int32 [B, k], top_p float32 [B, k]), larger logit first, equal logits: higher index first; the workspace is allocated
+        here, of the size the library's helper gives"""
+        B = u.shape[0]
+        top_idx = torch.empty((B, k), dtype=torch.int32, device=self.dev)
+        top_p = torch.empty((B, k), dtype=torch.float32, device=self.dev)
+        nbytes = int(abi.lib.qmann_answer_topk_i8_ws_bytes(C.byref(self.net), k, B))
+        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=self.dev)       # (torch allocations are 16-byte aligned)
+        abi.check(abi.lib.qmann_answer_topk_i8(C.byref(self.net), _ptr(w_ans_i8), abi.Fmt(*w_fmt), _ptr(u), _ptr(ws), nbytes, k,
+                                               _ptr(top_idx), _ptr(top_p), B, self._s()), "qmann_answer_topk_i8")
+        self._topk_i8_ws = ws                                                     # alive until the next call: the launch is asynchronous
+        return top_idx, top_p
+
     def forward_bow(self, story, question, row_off, max_slots, answer=None, taps=False):
         keys, vals, u0 = self.embed(story, question)
         r = self.hops(keys, vals, row_off, max_slots, u0, taps=taps)
