@@ -32,8 +32,10 @@
 //      scans, the workgroup also sums e^(x_r - Xb) over the rows retired so far, Xb the largest score the attention format
 //      can hold.  Once that sum passes 2^frac (1 + 2^-6) every read-out weight of the hop is known to quantise to code 0
 //      whatever the unread rows hold (derivation: ScanStop below): the wavefronts leave the scan, steps 2 and 3 are skipped
-//      and the hop continues with o = 0, the result the full scan would have produced.  Every wavefront posts its sum and
-//      looks at the workgroup's after each tile, in front of asking for another.
+//      and the hop continues with o = 0, the result the full scan would have produced.  This scan works in units of
+//      two loads per lane (half a tile), three per wavefront -- one being retired, two in flight: the lanes that retire
+//      a unit's rows add the rows' terms to the workgroup's sum, THEN the wavefront looks at that sum (its own unit included),
+//      and only then asks for another unit.
 #include "hops_mid.h"
 #include "hops_host.h"
 
@@ -47,64 +49,51 @@ namespace {
 // layer; sm_scaled is one float product, monotone in the code), and over any set P of rows already retired
 //     total >= sum_{r in P} e^(x_r - xmax) >= sum_{r in P} e^(x_r - Xb).
 // The sum on the right is what the scan accumulates -- in float, one v_exp_f32 per row (1 ulp, arguments <= 0, a flushed
-// denormal only lowers it), at most a few 10^4 additions (each within 6e-8 relative, 6e-4 in all even if every one rounded up) and
-// an exponent folded into one FMA (argument off by < 2e-5): the threshold 2^frac (1 + 2^-6) leaves 1.5 %, some twenty times
-// those errors together, and puts 1 / total far enough below 2^-frac that the float quotient cannot round up to it.  A NaN or
-// infinite scale makes the sum NaN, which never compares >= thr: such a hop runs the full path.
-// Posting and looking are two things (hops_common.h::scan_rows calls both once per tile).  post(): the lanes' sums meet in lane
-// 63 through six DPP steps (four v_add_f32_dpp within the rows of 16 lanes, two row broadcasts of a v_mov_b32_dpp and a
-// v_add_f32 each) and that lane adds them to one LDS float (ds_add_f32: nothing returned, nothing waited for).  peek(): a plain
-// LDS read of that word, issued when the tile's row sums are there; post() compares what it returned, behind the tile's
-// retiring, so that the read's latency hides under that arithmetic.  In all -- the masking of the one lane, the read, its wait
-// and the comparison included -- some 20 instructions per tile beside the 150 of the tile's arithmetic.
-// What a look sees is every wavefront's posts up to a tile ago -- a sum over retired rows like any other, only over fewer.  The
-// sum only grows, so the other wavefronts follow within a tile of their own, and the workgroup's decision behind the scan's
-// barrier -- the same LDS word, read by all -- is "zero" whenever any wavefront left.
+// denormal only lowers it), an exponent folded into one FMA (argument off by < 2e-5) and ONE addition per row into the
+// workgroup's float (each within 2^-24 relative; a term too small to move the sum only lowers it).  LDS holds at most 153 472
+// score bytes (hops_common.h's carve-up in 159 KB), so even if every addition rounded up the sum is high by less than
+// 153 472 . 2^-24 = 0.92 %: the threshold 2^frac (1 + 2^-6) leaves 1.5 %, so a sum that passes it stands for a true one above
+// 2^frac (1 + 0.6 %), which also puts 1 / total far enough below 2^-frac that the float quotient cannot round up to it.  A NaN
+// or infinite scale makes the sum NaN, which never compares >= thr: such a hop runs the full path.
+// Adding and looking (hops_common.h::scan_rows_stop looks once per unit, behind the unit's retiring).  add(): the lane that
+// retires a row adds the row's term to one LDS float (ds_add_f32: nothing returned, nothing waited for; the lanes of one
+// instruction that hit the one address are serialised by the LDS, not by the wavefront -- no cross-lane reduction, no VALU
+// work).  look(): a plain LDS read of that word, issued BEHIND the unit's adds.  The LDS operations of one wavefront complete
+// in order, so what the read returns includes the unit the wavefront has just retired -- the look is fresh -- and every add of
+// the other wavefronts that reached the LDS before it; its wait (lgkmcnt alone, no key load is waited for) and the comparison
+// follow at once, in front of the next request, and the read's latency is left to the other wavefronts of the SIMD to cover.
+// The order in which the lanes' terms arrive is not fixed, so the word's last bits differ from run to run; the decision's
+// RESULT does not: whichever way a hop decides, u is what the full scan gives (above).
+// The sum only grows, so the other wavefronts follow within a unit of their own, and the workgroup's decision behind the
+// scan's barrier -- the same LDS word, read by all -- is "zero" whenever any wavefront left.
 struct ScanStop {
     typedef __attribute__((address_space(3))) float lds_float;
-    float &lane_sum;          // this lane's e^(x_r - Xb) since the last post (the retire hook adds to it)
+    // the unit of the stopping scan: 16-byte loads per lane and request (half of kUnrollDefault: 16 rows at 128-byte rows, 8 at
+    // 256, 32 at 64), and units per wavefront -- one being retired, kDepth - 1 in flight
+    static constexpr int kUnitLoads = 2;
+    static constexpr int kDepth = 3;
     float *word;              // the workgroup's sum (LDS)
     float thr;
-    uint32_t lane;
-    template <int CTRL, int ROWS, bool BOUND>
-    static __device__ __forceinline__ float dpp_addf(float v)
+    // One retired row's e^(x_r - Xb) joins the workgroup's sum: the lane that retires the row adds it (ds_add_f32: nothing
+    // returned, nothing waited for).  Written out: as an atomicAdd the compiler wraps it in its loop over the active lanes.
+    // The compiler's wait counting cannot see this instruction.  Inside the scan that is harmless: LDS operations complete
+    // in order, so more of them in flight only make a counted wait stricter, and nothing there reads the word but look(),
+    // whose counted wait for its own read covers the adds in front of it.  INVARIANT: every way from scan_rows to the barrier
+    // behind the scan, or to any other read of the word, goes through flush(), which waits for the adds by hand -- the kernel
+    // calls it on its one path between the scan and that barrier, whichever way a wavefront left the scan.
+    static __device__ __forceinline__ void add(float *word, float v)
     {
-        return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, ROWS, 0xF, BOUND));
-    }
-    // `seen`: what peek() returned for this tile.  The add is written out: as an atomicAdd the compiler wraps it in its loop
-    // over the active lanes, for the one lane there is.  The compiler's wait counting cannot see this instruction.  Inside the
-    // scan that is harmless: LDS operations complete in order, so one more of them in flight only makes a counted wait stricter,
-    // and nothing there reads the word but peek(), which may see any earlier state.  INVARIANT: every way from scan_rows to the
-    // barrier behind the scan, or to any other read of the word, goes through flush(), which waits for the add by hand -- the
-    // kernel calls it on its one path between the scan and that barrier, whichever way a wavefront left the scan.
-    // (The comparison stands in front of the add, so that its wait is for the read alone.)
-    __device__ __forceinline__ bool post(float seen)
-    {
-        float v = lane_sum;
-        lane_sum = 0.0f;
-        v = dpp_addf<0xB1, 0xF, true>(v);            // quad_perm [1,0,3,2]
-        v = dpp_addf<0x4E, 0xF, true>(v);            // quad_perm [2,3,0,1]
-        v = dpp_addf<0x141, 0xF, true>(v);           // row_half_mirror
-        v = dpp_addf<0x140, 0xF, true>(v);           // row_mirror: every lane holds its row's sum
-        v = dpp_addf<0x142, 0xA, false>(v);          // row_bcast:15 into rows 1 and 3 (the others add 0)
-        v = dpp_addf<0x143, 0xC, false>(v);          // row_bcast:31 into rows 2 and 3: lane 63 holds the wavefront's sum
-        const bool leave = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, seen))) >= thr;
         const uint32_t at = (uint32_t)(__UINTPTR_TYPE__)(lds_float *)word;
-        if (lane == 63u) asm volatile("ds_add_f32 %0, %1" : : "v"(at), "v"(v) : "memory");
-        return leave;
+        asm volatile("ds_add_f32 %0, %1" : : "v"(at), "v"(v) : "memory");
     }
-    // what the lanes still hold, behind the scan
-    __device__ __forceinline__ void flush()
+    // behind the scan
+    static __device__ __forceinline__ void flush() { asm volatile("s_waitcnt lgkmcnt(0)" : : : "memory"); }
+    // the workgroup's sum with this wavefront's last unit in it: leave? (an address-space-3 load: a generic pointer would make
+    // it a flat load, which waits for every key load in flight; volatile keeps it behind the retire hook's adds)
+    __device__ __forceinline__ bool look() const
     {
-        (void)post(0.0f);
-        asm volatile("s_waitcnt lgkmcnt(0)" : : : "memory");
-    }
-    // `dep`: a value the read has to wait for (no instruction: the index is 0, but the compiler cannot know it)
-    __device__ __forceinline__ float peek(int dep) const
-    {
-        uint32_t i = 0;
-        asm("; ScanStop::peek behind %1" : "+v"(i) : "v"(dep));
-        return ((const volatile lds_float *)(lds_float *)word)[i];
+        const float seen = *(const volatile lds_float *)(lds_float *)word;
+        return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, seen))) >= thr;
     }
 };
 
@@ -156,7 +145,7 @@ k_hops_fixed(const HopArgs a, const StoryTop<TOP> tp)
         if (tid == 0) misc[0] = 0u;
         // the bound of step 1b: e^(x - Xb) = 2^(code . stop_k1 + stop_k0)
         float *stop_word = (float *)(misc + 1);
-        float stop_thr = 0.0f, stop_k1 = 0.0f, stop_k0 = 0.0f, stop_sum = 0.0f;
+        float stop_thr = 0.0f, stop_k1 = 0.0f, stop_k0 = 0.0f;
         if constexpr (STOP) {
             const SmCfg smc = sm_cfg(a, h);
             const float top = qm_scale_down((float)maxm, fm.frac), log2e = 1.44269504f;
@@ -181,17 +170,16 @@ k_hops_fixed(const HopArgs a, const StoryTop<TOP> tp)
                 const int code = v > maxm ? maxm : (v < -maxm ? -maxm : v);
                 sc[r] = (int8_t)code;
                 atomicAdd(&hw[code + 127], 1u);
-                if constexpr (STOP) stop_sum += __builtin_amdgcn_exp2f(__builtin_fmaf((float)code, stop_k1, stop_k0));
+                if constexpr (STOP) ScanStop::add(stop_word, __builtin_amdgcn_exp2f(__builtin_fmaf((float)code, stop_k1, stop_k0)));
             };
             if (S < (kWave / LPR) * kUnroll) scan_rows_short<LPR>(kb, S, row_sum, retire, lane, wave, nwaves);
             else if (STOP || nwaves == kWaves) {        // (a stopping launch always has four wavefronts)
-                if constexpr (STOP) scan_rows<LPR, kUnroll, NT, kWaves>(kb, S, row_sum, retire, lane, wave, ScanStop{stop_sum, stop_word, stop_thr, lane});
+                if constexpr (STOP) scan_rows<LPR, kUnroll, NT, kWaves>(kb, S, row_sum, retire, lane, wave, ScanStop{stop_word, stop_thr});
                 else scan_rows<LPR, kUnroll, NT, kWaves>(kb, S, row_sum, retire, lane, wave);
             }
             else scan_rows<LPR, kUnroll, NT, 1>(kb, S, row_sum, retire, lane, wave);
-            // what the lanes still hold (the short scan posts nothing), and the wait for every post (ScanStop's invariant): the
-            // decision below is taken on the whole sum
-            if constexpr (STOP) ScanStop{stop_sum, stop_word, stop_thr, lane}.flush();
+            // the wait for every add (ScanStop's invariant): the decision below is taken on the whole sum
+            if constexpr (STOP) ScanStop::flush();
         }
         __syncthreads();
         // every weight code of this hop is 0 (ScanStop above): no softmax, no survivors, o = 0.  All threads read the one word.

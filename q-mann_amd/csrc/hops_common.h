@@ -266,18 +266,78 @@ __device__ __forceinline__ void scan_rows_short(const uint8_t *__restrict__ kb, 
 // scan_rows' stop hook when the caller has none: no code
 struct ScanNoStop {};
 
+// scan_rows with a stop hook.  The hook names its own UNIT -- Stop::kUnitLoads 16-byte loads per lane, UNIT = kUnitLoads x
+// (64 / LPR) rows: what a wavefront requests, retires and decides on at a time -- and its depth, Stop::kDepth units per
+// wavefront: one being retired, the others in flight.  Units go to the NW wavefronts in turn, as scan_rows' tiles do.  Per unit:
+// row sums, retire (the caller's hook; it also hands the rows' share of the stop's sum over), THEN stop.look() -- which sees
+// that share and whatever the other wavefronts have handed over -- and, if it says so (wavefront-uniform), the wavefront leaves BEFORE it asks
+// for the unit kDepth ahead: the kDepth - 1 units then in flight are dropped.  A unit that would run past the last row is
+// moved back to end at row S (needs S >= UNIT; the caller sends shorter memories to scan_rows_short); a unit behind the last
+// one is asked for like the others -- its start moved back into range too -- and never retired.
+template <int LPR, bool NT, int NW, typename RowSum, typename Retire, typename Stop>
+__device__ __forceinline__ void scan_rows_stop(const uint8_t *__restrict__ kb, uint32_t S, RowSum row_sum, Retire retire,
+                                               uint32_t lane, uint32_t wave, Stop stop)
+{
+    constexpr int UN = Stop::kUnitLoads, DEPTH = Stop::kDepth;
+    constexpr uint32_t RPW = kWave / LPR;          // rows per wavefront instruction
+    constexpr uint32_t UNIT = RPW * UN;
+    constexpr uint32_t Dp = LPR * 16;
+    constexpr uint32_t STEP = NW * UNIT;
+    const uint32_t sub = lane / LPR, chunk = lane % LPR;
+    const uint32_t n_units = (S + UNIT - 1) / UNIT;
+    const uint8_t *lane_base = kb + chunk * 16;
+    if (wave >= n_units) return;
+
+    auto unit_start = [&](uint32_t base) { return base + UNIT <= S ? base : S - UNIT; };
+    auto issue = [&](i32x4 (&x)[UN], uint32_t base) {
+        const uint8_t *p = lane_base + (size_t)(unit_start(base) + sub) * Dp;
+#pragma unroll
+        for (int j = 0; j < UN; j++) x[j] = load16<NT>(p + (size_t)j * RPW * Dp);
+    };
+    // scan_rows' `reduce` with the hook's look behind it (with UN < LPR some lanes hold no row of the unit: j >= UN)
+    auto step = [&](const i32x4 (&x)[UN], uint32_t at) {
+        int s[UN];
+#pragma unroll
+        for (int j = 0; j < UN; j++) s[j] = row_lanes_sum<LPR>(row_sum(x[j]));
+        const uint32_t start = unit_start(at);
+#pragma unroll
+        for (int j0 = 0; j0 < UN; j0 += LPR) {
+            int v = s[j0];
+#pragma unroll
+            for (int t = 1; t < LPR && j0 + t < UN; t++) v = (chunk == (uint32_t)t) ? s[j0 + t] : v;
+            const uint32_t j = j0 + chunk;
+            const uint32_t r = start + j * RPW + sub;
+            if (j < (uint32_t)UN && r >= at) retire(r, v);
+        }
+        return stop.look();
+    };
+
+    i32x4 x[DEPTH][UN];
+    uint32_t base = wave * UNIT;
+#pragma unroll
+    for (int d = 0; d < DEPTH; d++) issue(x[d], base + d * STEP);
+    for (uint32_t t = wave;;) {
+#pragma unroll
+        for (int d = 0; d < DEPTH; d++) {
+            if (step(x[d], base + d * STEP) || (t += NW) >= n_units) return;
+            issue(x[d], base + (DEPTH + d) * STEP);
+        }
+        base += DEPTH * STEP;
+    }
+}
+
 // One wavefront streams tiles of UN x (64 / LPR) rows; loads of the next tile are issued before
 // the current one is reduced (addresses are clamped to the last row instead of being predicated,
 // so the loop body has no divergent control flow and the compiler can count its vmcnt waits).
-// `stop` (any type but ScanNoStop; the loop is then the second one below, same tiles in the same order): once a tile's row sums
-// are complete the wavefront calls stop.peek(dep) -- `dep` one of those sums, so that the hook can tie its read behind the
-// tile's arrival --, retires the tile, hands what peek returned to stop.post(), and leaves if that says so (wavefront-uniform),
-// BEFORE it asks for the tile after next: the one tile then in flight is dropped (its addresses were in range like every
-// other tile's).
+// `stop` (any type but ScanNoStop): scan_rows_stop above, in the hook's own unit.
 template <int LPR, int UN, bool NT, int NW, typename RowSum, typename Retire, typename Stop = ScanNoStop>
 __device__ __forceinline__ void scan_rows(const uint8_t *__restrict__ kb, uint32_t S, RowSum row_sum, Retire retire,
                                           uint32_t lane, uint32_t wave, Stop stop = Stop{})
 {
+    if constexpr (!std::is_same<Stop, ScanNoStop>::value) {
+        scan_rows_stop<LPR, NT, NW>(kb, S, row_sum, retire, lane, wave, stop);
+        return;
+    }
     constexpr uint32_t nwaves = NW;                // wavefronts sharing the rows of this query
     constexpr uint32_t RPW = kWave / LPR;          // rows per wavefront instruction
     constexpr uint32_t TILE = RPW * UN;            // rows per wavefront iteration
@@ -318,37 +378,6 @@ __device__ __forceinline__ void scan_rows(const uint8_t *__restrict__ kb, uint32
     uint32_t base = wave * TILE;
     constexpr uint32_t STEP = nwaves * TILE;
     issue(xa, base);
-    if constexpr (!std::is_same<Stop, ScanNoStop>::value) {
-        // the loop below turned by half a step, so that a wavefront decides between retiring a tile and asking for the next but
-        // one; a tile behind the last is asked for like the others (its start is moved back into range) and never retired.
-        // step: `reduce` with the hook's two calls in it
-        auto step = [&](const i32x4 (&x)[UN], uint32_t at) {
-            int s[UN];
-#pragma unroll
-            for (int j = 0; j < UN; j++) s[j] = row_lanes_sum<LPR>(row_sum(x[j]));
-            const auto seen = stop.peek(s[UN - 1]);
-            const uint32_t start = tile_start(at);
-#pragma unroll
-            for (int j0 = 0; j0 < UN; j0 += LPR) {
-                int v = s[j0];
-#pragma unroll
-                for (int t = 1; t < LPR && j0 + t < UN; t++) v = (chunk == (uint32_t)t) ? s[j0 + t] : v;
-                const uint32_t j = j0 + chunk;
-                const uint32_t r = start + j * RPW + sub;
-                if (j < (uint32_t)UN && r >= at) retire(r, v);
-            }
-            return stop.post(seen);
-        };
-        issue(xb, base + STEP);
-        for (uint32_t t = wave;;) {
-            if (step(xa, base) || (t += nwaves) >= n_tiles) break;
-            issue(xa, base + 2 * STEP);
-            if (step(xb, base + STEP) || (t += nwaves) >= n_tiles) break;
-            issue(xb, base + 3 * STEP);
-            base += 2 * STEP;
-        }
-        return;
-    }
     for (uint32_t t = wave; t < n_tiles; t += 2 * nwaves) {
         issue(xb, base + STEP);
         reduce(xa, base);
