@@ -151,12 +151,32 @@ int qmann_hops_i8(const qmann_net *net, const int8_t *keys, const int8_t *vals, 
  * csrc/batch_hops_shared.hip); the library chooses the tile, QMANN_SHARED_QT (environment) forces one that fits.
  * attention_mode QMANN_ATT_FIXED only -- every qmann_net field qmann_hops_i8 honours in that mode is honoured; any other
  * attention mode returns QMANN_EUNSUPPORTED with nothing launched (Hamming V0 / V1 on packed codes: qmann_hops_shared_packed
- * below; the APPX and float forms are follow-ups).
+ * below; float attention: qmann_hops_shared_float_i8 below; the APPX form is a follow-up).
  * n_slots = 0: QMANN_EINVAL.  A memory too long for LDS with one query per workgroup: QMANN_ERANGE (sizing helper below).
  * One ordered step on `stream`, no second stream, no library scratch: it can be captured in a graph. */
 int qmann_hops_shared_i8(const qmann_net *net, const int8_t *keys, const int8_t *vals, size_t hop_stride,
                          uint32_t n_slots, const float *u0, float *u_out, const qmann_taps *taps,
                          uint32_t n_query, void *stream);
+
+/* qmann_hops_shared_i8 for float attention (QMANN_ATT_FLOAT, csrc/batch_hops_shared_float.hip).  Layout as qmann_hops_shared_i8:
+ * keys, vals int8 [n_hop][n_slots][Dp] sign-magnitude carrying Q(w[h]) codes, as qmann_hops_i8 documents for mode 1; hop_stride
+ * bytes between hop planes, 0 = tied hops; u0 / u_out [n_query][D].  taps (any pointer may be NULL): score_codes / scores / probs
+ * [n_hop][n_query][n_slots], o / u [n_query][n_hop][D], allowed with hop_stride = 0.
+ * u_out and EVERY tap are bit-equal to qmann_hops_i8 with attention_mode = QMANN_ATT_FLOAT on n_query copies of the planes
+ * (row_off[q] = q . n_slots, max_slots = n_slots): one workgroup owns a tile of 1, 2, 4 or 8 queries, scans the key plane and
+ * reads the value plane once per hop for all of them, and keeps every query's float additions in the per-story kernel's order.
+ * Every qmann_net field qmann_hops_i8 honours in this mode is honoured (the three softmax bases, the shift-based normaliser,
+ * en_att_scale, en_non_linearity, binary u, en_lin_map off, per-hop formats).  The library chooses the tile, QMANN_SHARED_QT
+ * forces one that fits.
+ * Refusals, with nothing launched and no output touched, in this order: those of qmann_hops_shared_i8's argument and format
+ * checks; QMANN_EUNSUPPORTED for any attention mode but QMANN_ATT_FLOAT (and for a dim_emb_pad outside {64, 128, 256});
+ * QMANN_EINVAL for n_slots = 0; QMANN_ERANGE for a memory whose float-per-slot LDS exceeds 160 KiB - 1 KiB with one query per
+ * workgroup (more than 38 368 slots; sizing helper below -- a slot-split float form for longer memories is out of scope);
+ * QMANN_OK for n_query = 0; QMANN_ERANGE for 2^24 queries or more.
+ * One kernel on `stream`, no second stream, no scratch, no allocation: it can be captured in a graph. */
+int qmann_hops_shared_float_i8(const qmann_net *net, const int8_t *keys, const int8_t *vals, size_t hop_stride,
+                               uint32_t n_slots, const float *u0, float *u_out, const qmann_taps *taps,
+                               uint32_t n_query, void *stream);
 
 /* qmann_hops_shared_i8 with the SLOTS cut into slices (csrc/batch_hops_shared_split.hip): for memories too long for LDS (up to
  * 2^24 slots) and for batches of so few questions that one workgroup per tile of queries leaves most compute units idle.
@@ -483,6 +503,12 @@ size_t qmann_hops_shared_lds_bytes(uint32_t n_slots, uint32_t queries_per_group)
 /* queries per workgroup qmann_hops_shared_i8 would take for this call on the current device, QMANN_SHARED_QT included
  * (1, 2, 4 or 8; 0 where the call would launch nothing) -- for tests and timing tools that must know which tile ran */
 uint32_t qmann_hops_shared_tile(uint32_t n_slots, uint32_t n_query);
+
+/* the same two for qmann_hops_shared_float_i8, which keeps a float per slot and query:
+ * queries_per_group . (qmann_hops_lds_bytes(0) + 4 . n_slots rounded up to 16); within 160 KiB - 1 KiB for one query (up to
+ * 38 368 slots) or the call returns QMANN_ERANGE; the tile is 0 where the call would launch nothing */
+size_t qmann_hops_shared_float_lds_bytes(uint32_t n_slots, uint32_t queries_per_group);
+uint32_t qmann_hops_shared_float_tile(uint32_t n_slots, uint32_t n_query);
 
 /* the same two for qmann_hops_shared_packed, whose LDS depends on the net (V0 keeps tables of num_bit . dim_emb + 1 bins per
  * query): bytes of one workgroup that owns `queries_per_group` queries (within 160 KiB - 1 KiB for one query, or the call

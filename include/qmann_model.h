@@ -123,8 +123,8 @@ int qmann_model_forward_shared_words(qmann_model *m, const uint16_t *story_words
  * qmann_model_memorize_words: story_words [n_rows][max_words] as above.  Embeds every hop's memory (one plane when the hops are
  * tied) into buffers the model owns BESIDE its per-batch workspace -- qmann_model_forward_words / _bow / _shared_words calls in
  * between do not disturb them -- and replaces an earlier memory.  Attention modes QMANN_ATT_FIXED (asks run qmann_hops_shared_i8)
- * and QMANN_ATT_HAMMING_V0 / _V1 (packed planes, qmann_hops_shared_packed); QMANN_ATT_FLOAT and _APPX return
- * QMANN_EUNSUPPORTED, and so does a Hamming model the packed call would refuse (num_bit outside {1, 2, 4, 8}; 64 padded columns
+ * and QMANN_ATT_HAMMING_V0 / _V1 (packed planes, qmann_hops_shared_packed); QMANN_ATT_FLOAT (unless
+ * qmann_model_enable_float_asks below has turned its asks on) and _APPX return QMANN_EUNSUPPORTED, and so does a Hamming model the packed call would refuse (num_bit outside {1, 2, 4, 8}; 64 padded columns
  * with one bit).  n_rows = 0: QMANN_EINVAL.  A memory too long for LDS with one query per workgroup: QMANN_ERANGE, here, so that
  * an ask cannot fail late.  A call that fails leaves the model with nothing memorised.
  *
@@ -152,7 +152,8 @@ uint32_t qmann_model_memory_rows(const qmann_model *m);
  * QMANN_ATT_FIXED models only: a Hamming V0 / V1 model returns QMANN_EUNSUPPORTED here and is served by
  * qmann_model_ask_words_top_packed below (its softmax is per slot (V1) or over up to 2 049 bins (V0), a different selection).
  * What qmann_model_ask_words refuses or answers without work is answered FIRST and as there (nothing memorised: QMANN_EINVAL;
- * n_query = 0: QMANN_OK whatever k; null question_words or pred: QMANN_EINVAL); then QMANN_EUNSUPPORTED for a Hamming model; then QMANN_EINVAL for k = 0,
+ * n_query = 0: QMANN_OK whatever k; null question_words or pred: QMANN_EINVAL); then QMANN_EUNSUPPORTED for a Hamming model
+ * and for a QMANN_ATT_FLOAT model (float attention has no attended-slots form), ahead of any launch; then QMANN_EINVAL for k = 0,
  * k > QMANN_MAX_TOP_SLOTS, a null top_slot or top_p.  A refused call launches nothing and leaves every output as it was. */
 int qmann_model_ask_words_top(qmann_model *m, const uint16_t *question_words, uint32_t max_q_words, uint32_t n_query,
                               const uint32_t *answer, uint32_t *pred, float *cost, uint32_t *match,
@@ -165,8 +166,8 @@ int qmann_model_ask_words_top(qmann_model *m, const uint16_t *question_words, ui
  * match, qmann_model_last_u and what qmann_model_last_topk ranks are those of qmann_model_ask_words; nothing is allocated once
  * the question workspace has its size, so the call can be captured in a graph and replayed.
  * What qmann_model_ask_words refuses or answers without work is answered FIRST and as there; then QMANN_EUNSUPPORTED for a
- * QMANN_ATT_FIXED model (qmann_model_ask_words_top serves those); then QMANN_EINVAL for k = 0, k > QMANN_MAX_TOP_SLOTS, a null
- * top_slot or top_p.  A refused call launches nothing and leaves every output as it was. */
+ * QMANN_ATT_FIXED model (qmann_model_ask_words_top serves those) and for a QMANN_ATT_FLOAT model; then QMANN_EINVAL for k = 0,
+ * k > QMANN_MAX_TOP_SLOTS, a null top_slot or top_p.  A refused call launches nothing and leaves every output as it was. */
 int qmann_model_ask_words_top_packed(qmann_model *m, const uint16_t *question_words, uint32_t max_q_words, uint32_t n_query,
                                      const uint32_t *answer, uint32_t *pred, float *cost, uint32_t *match,
                                      uint32_t k, uint32_t *top_slot, float *top_p, void *stream);
@@ -190,6 +191,20 @@ int qmann_model_enable_split_asks(qmann_model *m, size_t scratch_bytes, void *st
  * floor(budget / share) questions; a memory that fits LDS is asked as before, bit for bit.  scratch_bytes = 0 turns the mode off
  * and forgets a memory that can no longer be asked.  Any other model: QMANN_EUNSUPPORTED. */
 int qmann_model_enable_split_asks_packed(qmann_model *m, size_t scratch_bytes, void *stream);
+
+/* Opt-in for QMANN_ATT_FLOAT models (the reference's ATTENTION_MODE 1): memorise once, ask many through
+ * qmann_hops_shared_float_i8 (qmann_batch.h).  Without this call such a model is refused by qmann_model_memorize_words as
+ * described above.  With on != 0, qmann_model_memorize_words embeds a float model's memory on the weight grid, as
+ * qmann_model_forward_words does for such a model (one plane when the hops are tied), and checks its length against
+ * qmann_hops_shared_float_lds_bytes(n_rows, 1): beyond 160 KiB - 1 KiB (38 368 rows) it returns QMANN_ERANGE -- at memorize,
+ * never at ask.  qmann_model_ask_words then gives the same pred, cost, match and qmann_model_last_u as
+ * qmann_model_forward_words on n_query copies of the story, bit for bit (cost: up to the order of its float atomics), allocates
+ * nothing once the question workspace has its size, and can be captured in a graph; qmann_model_last_topk works after it.
+ * qmann_model_ask_words_top / _top_packed keep returning QMANN_EUNSUPPORTED for such a model, before anything is launched, and
+ * so do qmann_model_forward_shared_words and both qmann_model_enable_split_asks calls.
+ * on = 0 forgets a memorised memory and restores the behaviour above exactly.  The call allocates nothing.
+ * Any model whose attention mode is not QMANN_ATT_FLOAT: QMANN_EUNSUPPORTED. */
+int qmann_model_enable_float_asks(qmann_model *m, int on);
 
 /* Forward from the reference's float bag-of-words pools (dev_m_test / dev_q_test, MemN2N.c:2337-2349):
  *   story [rows_total][dim_input] float, question [n_query][dim_input] float. */

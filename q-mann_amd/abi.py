@@ -169,6 +169,10 @@ _proto("qmann_hops_shared_i8", C.c_int, [C.POINTER(Net), _vp, _vp, C.c_size_t, C
 _proto("qmann_pack_bitplanes", C.c_int, [_vp, _vp, C.c_size_t, C.c_uint32, C.c_uint32, _vp])
 _proto("qmann_hops_packed", C.c_int, [C.POINTER(Net), _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_uint32, _vp, _vp,
                                       C.POINTER(Taps), C.c_uint32, _vp])
+_proto("qmann_hops_shared_float_lds_bytes", C.c_size_t, [C.c_uint32, C.c_uint32])
+_proto("qmann_hops_shared_float_tile", C.c_uint32, [C.c_uint32, C.c_uint32])
+_proto("qmann_hops_shared_float_i8", C.c_int, [C.POINTER(Net), _vp, _vp, C.c_size_t, C.c_uint32, _vp, _vp,
+                                               C.POINTER(Taps), C.c_uint32, _vp])
 _proto("qmann_hops_shared_split_ws_bytes", C.c_size_t, [C.POINTER(Net), C.c_uint32, C.c_uint32])
 _proto("qmann_hops_shared_split_slices", C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32])
 _proto("qmann_hops_shared_split_i8", C.c_int, [C.POINTER(Net), _vp, _vp, C.c_size_t, C.c_uint32, _vp, _vp,
@@ -243,6 +247,7 @@ _proto("qmann_model_memory_rows", C.c_uint32, [_vp])
 _proto("qmann_model_forward_bow", C.c_int, [_vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, _vp])
 _proto("qmann_model_enable_split_asks", C.c_int, [_vp, C.c_size_t, _vp])
 _proto("qmann_model_enable_split_asks_packed", C.c_int, [_vp, C.c_size_t, _vp])
+_proto("qmann_model_enable_float_asks", C.c_int, [_vp, C.c_int])
 _proto("qmann_model_last_u", _vp, [_vp])
 _proto("qmann_model_last_topk", C.c_int, [_vp, C.c_uint32, _vp, _vp, _vp])
 _proto("qmann_model_last_n_query", C.c_uint32, [_vp])

@@ -102,6 +102,8 @@ struct qmann_model {
     // attention mode, hence one of the two), allocated by that call and never inside an ask; split_bytes = 0: the mode is off
     void *split_ws = nullptr;
     size_t split_bytes = 0;
+    // qmann_model_enable_float_asks: a QMANN_ATT_FLOAT model may memorise a memory and ask it through qmann_hops_shared_float_i8
+    bool float_asks = false;
     uint32_t last_n_query = 0;   // queries of the last forward that enqueued an answer layer (qmann_model_last_topk ranks m->u's rows)
     bool answer_exact = false;   // rt.h::qm_model_answer_exact: the float answer layer keeps the serial order of additions
 };
@@ -152,6 +154,7 @@ bool packed_model_ok(const qmann_model *m)
 // one query's LDS in the unsplit shared-plane call of the model's mode, and its share of a split call's workspace
 size_t ask_lds_bytes(const qmann_model *m, uint32_t n_rows)
 {
+    if (m->net.attention_mode == QMANN_ATT_FLOAT) return qmann_hops_shared_float_lds_bytes(n_rows, 1);      // (a float per slot)
     return packed_mode(m->net) ? qmann_hops_shared_packed_lds_bytes(&m->net, n_rows, 1) : qmann_hops_shared_lds_bytes(n_rows, 1);
 }
 size_t ask_split_share(const qmann_model *m, uint32_t n_rows)
@@ -624,7 +627,8 @@ int qmann_model_memorize_words(qmann_model *m, const uint16_t *story_words, uint
     if (!m) return QMANN_EINVAL;
     const qmann_net &n = m->net;
     const bool packed = packed_mode(n);
-    if (!packed && n.attention_mode != QMANN_ATT_FIXED) return QMANN_EUNSUPPORTED;      // (what the shared-plane hop calls cover)
+    const bool fl = n.attention_mode == QMANN_ATT_FLOAT && m->float_asks;           // (qmann_model_enable_float_asks)
+    if (!packed && !fl && n.attention_mode != QMANN_ATT_FIXED) return QMANN_EUNSUPPORTED;      // (what the shared-plane hop calls cover)
     if (packed && !packed_model_ok(m)) return QMANN_EUNSUPPORTED;       // what qmann_hops_shared_packed would refuse, said here
     if (!story_words || n_rows == 0) return QMANN_EINVAL;
     // the memory's length against LDS now, so that an ask cannot fail late
@@ -668,6 +672,7 @@ static int ask_words_impl(qmann_model *m, const uint16_t *question_words, uint32
     m->last_n_query = 0;                                // (set again where this call succeeds)
     if (!question_words || !pred) return QMANN_EINVAL;
     if (top) {                                          // behind the base call's refusals, and here: an ask must not fail behind its embedding
+        if (m->net.attention_mode == QMANN_ATT_FLOAT) return QMANN_EUNSUPPORTED;          // (float attention has no attended-slots form)
         if (packed_mode(m->net) != (top == kAskTopPacked)) return QMANN_EUNSUPPORTED;     // each form serves its own models
         if (k == 0 || k > QMANN_MAX_TOP_SLOTS || !top_slot || !top_p) return QMANN_EINVAL;
     }
@@ -699,7 +704,9 @@ static int ask_words_impl(qmann_model *m, const uint16_t *question_words, uint32
                         : qmann_hops_shared_split_i8(&m->net, m->mem_keys, m->mem_vals, plane, S, u0, u, nullptr, nq, 0, m->split_ws,
                                                      m->split_bytes, stream);
         }
-    } else if (packed && top)
+    } else if (m->net.attention_mode == QMANN_ATT_FLOAT)
+        rc = qmann_hops_shared_float_i8(&m->net, m->mem_keys, m->mem_vals, plane, S, m->u0, m->u, nullptr, n_query, stream);
+    else if (packed && top)
         rc = qmann_hops_shared_top_packed(&m->net, m->mem_planes, key_plane, m->mem_vals, plane, S, m->u0, m->u, k, top_slot, top_p,
                                           n_query, stream);
     else if (packed)
@@ -745,6 +752,15 @@ int qmann_model_enable_split_asks(qmann_model *m, size_t scratch_bytes, void *st
     DeviceScope on(m->device);
     const int rc = set_split_workspace(m, scratch_bytes, stream);
     return rc ? rc : qm_scope.rc();
+}
+
+int qmann_model_enable_float_asks(qmann_model *m, int on)
+{
+    if (!m) return QMANN_EINVAL;
+    if (m->net.attention_mode != QMANN_ATT_FLOAT) return QMANN_EUNSUPPORTED;
+    m->float_asks = on != 0;
+    if (!on) m->mem_rows = 0;                                // off: the memory is forgotten, memorize_words refuses again
+    return QMANN_OK;
 }
 
 int qmann_model_enable_split_asks_packed(qmann_model *m, size_t scratch_bytes, void *stream)

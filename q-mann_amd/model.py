@@ -310,6 +310,31 @@ class QNet:
                   "qmann_hops_shared_i8")
         return (u_out, tobj) if taps else u_out
 
+    def hops_shared_float(self, keys, vals, n_slots, u0, taps=False, u_out=None):
+        """qmann_hops_shared_float_i8: hops_shared for float attention (attention_mode 1).  keys/vals int8 [H][n_slots][Dp], or
+        [1][n_slots][Dp] for tied hops (hop stride 0), on the weight grid; u0 [B][D] float.  taps: score_codes / scores / probs
+        [H][B][n_slots], o / u [B][H][D]."""
+        B = u0.shape[0]
+        assert keys.shape in ((self.H, n_slots, self.Dp), (1, n_slots, self.Dp)) and vals.shape == keys.shape
+        assert keys.is_contiguous() and vals.is_contiguous()
+        if u_out is None:
+            u_out = torch.empty_like(u0)
+        tp, tobj = None, None
+        if taps:
+            tobj = HopTaps(
+                torch.zeros((self.H, B, n_slots), dtype=torch.int32, device=self.dev),
+                torch.zeros((self.H, B, n_slots), dtype=torch.float32, device=self.dev),
+                torch.zeros((self.H, B, n_slots), dtype=torch.float32, device=self.dev),
+                torch.zeros((B, self.H, self.D), dtype=torch.float32, device=self.dev),
+                torch.zeros((B, self.H, self.D), dtype=torch.float32, device=self.dev))
+            tp = abi.Taps(tobj.score_codes.data_ptr(), tobj.scores.data_ptr(), tobj.probs.data_ptr(),
+                          tobj.o.data_ptr(), tobj.u.data_ptr())
+        hop_stride = n_slots * self.Dp if keys.shape[0] == self.H else 0          # one plane for several hops: tied
+        abi.check(abi.lib.qmann_hops_shared_float_i8(C.byref(self.net), _ptr(keys), _ptr(vals), hop_stride, n_slots, _ptr(u0),
+                                                     _ptr(u_out), C.byref(tp) if tp else None, B, self._s()),
+                  "qmann_hops_shared_float_i8")
+        return (u_out, tobj) if taps else u_out
+
     def hops_shared_split(self, keys, vals, n_slots, u0, n_slices=0, taps=False, u_out=None):
         """qmann_hops_shared_split_i8: hops_shared with the slots cut into n_slices slices (0: the library's choice); the
         workspace is allocated here, of the size the library's helper gives.  Arguments, results and taps as hops_shared."""
@@ -687,6 +712,11 @@ class HostModel:
         go through the slot-split hops on packed codes); 0 turns the mode off"""
         abi.check(abi.lib.qmann_model_enable_split_asks_packed(self.h, int(nbytes), self._s()),
                   "qmann_model_enable_split_asks_packed")
+
+    def enable_float_asks(self, on=True):
+        """qmann_model_enable_float_asks: a float-attention model (attention_mode 1) may memorize_words and ask_words (through
+        qmann_hops_shared_float_i8); on=False forgets the memory and turns the mode off"""
+        abi.check(abi.lib.qmann_model_enable_float_asks(self.h, 1 if on else 0), "qmann_model_enable_float_asks")
 
     def memory_rows(self) -> int:
         return int(abi.lib.qmann_model_memory_rows(self.h))
