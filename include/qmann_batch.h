@@ -256,6 +256,40 @@ int qmann_hops_top_i8(const qmann_net *net, const int8_t *keys, const int8_t *va
                       const uint32_t *row_off, uint32_t max_slots, const float *u0, float *u_out,
                       uint32_t k, uint32_t *top_slot, float *top_p, uint32_t n_query, void *stream);
 
+/* Attended slots for float attention (QMANN_ATT_FLOAT, csrc/batch_hops_top_float.hip): qmann_hops_i8 (every query its own
+ * memory) and qmann_hops_shared_float_i8 (one memory for all queries) that also return, per query and hop, the k memory rows the
+ * hop weighted most and their weights, without a probability array anywhere -- in this mode p is not quantised, every slot
+ * carries weight, and the `probs` tap is the largest array the library can be asked to write.
+ *   top_slot [n_query][n_hop][k] uint32, top_p [n_query][n_hop][k] float, device memory; 1 <= k <= QMANN_MAX_TOP_SLOTS.
+ * qmann_hops_top_float_i8, in terms of what qmann_hops_i8 (attention_mode = QMANN_ATT_FLOAT) writes to taps.probs for the same
+ * arguments, with r0 = row_off[q] and S = min(row_off[q+1] - r0, max_slots): row (q, h) lists the slots s in [0, S) -- counted
+ * from the story's first row -- that come first in the order "larger probability first, equal probabilities: lower slot first",
+ * and top_p[q][h][j] is bit-equal to probs[h][r0 + top_slot[q][h][j]].  qmann_hops_shared_top_float_i8, in terms of what
+ * qmann_hops_shared_float_i8 writes for the same arguments: S = n_slots, and top_p[q][h][j] is bit-equal to
+ * probs[h][q][top_slot[q][h][j]], under every query tile (QMANN_SHARED_QT).
+ * The order is over the probability VALUES, as floats: slots tie where their probabilities are equal floats (equal rows,
+ * underflow to 0, att_scale = 0); a negative att_scale needs no rule of its own; a NaN probability -- the shift-based normaliser
+ * divides by llrint(log2(total)), which is 0 for a total below sqrt 2, and 0 / 0 is then reached by every slot whose e^x
+ * underflowed -- ranks below every number (+inf, the other quotient by 0, ranks above).  Entries past S hold slot 0xFFFFFFFF and
+ * p 0.0f: an empty story, k > S, a story cut by max_slots (no slot >= max_slots appears).
+ * u_out is bit-equal to the base call's, and every qmann_net field the base call honours is honoured (the three softmax bases,
+ * the shift-based normaliser, en_att_scale, en_non_linearity, binary u, en_lin_map off, per-hop formats).  hop_stride = 0 (tied
+ * hops) is allowed -- the outputs are indexed by query -- and gives the result of the call on n_hop copies of the plane.  There is
+ * no taps argument: a host that wants taps calls the base functions.
+ * The selection runs inside the hop kernel behind each query's softmax, over the floats the query's LDS slice holds
+ * (csrc/hops_attended_float.h): exact, no atomics, no scratch.  LDS per query, the 38 368-slot cap and the shared call's tile are
+ * the base calls'.  One kernel on `stream`: no second stream, no library scratch, no allocation -- it can be captured in a graph.
+ * Nothing is launched, no output is touched and the code returned is: whatever the base call answers for the same arguments
+ * without taps, unchanged and FIRST (its refusals; n_query = 0 is QMANN_OK whatever k); then QMANN_EUNSUPPORTED for any
+ * attention mode but QMANN_ATT_FLOAT; then QMANN_EINVAL for k = 0, k > QMANN_MAX_TOP_SLOTS, a null top_slot or top_p.
+ * (qmann_hops_top_i8 and the other attended-slots calls keep refusing QMANN_ATT_FLOAT as documented above.) */
+int qmann_hops_top_float_i8(const qmann_net *net, const int8_t *keys, const int8_t *vals, size_t hop_stride,
+                            const uint32_t *row_off, uint32_t max_slots, const float *u0, float *u_out,
+                            uint32_t k, uint32_t *top_slot, float *top_p, uint32_t n_query, void *stream);
+int qmann_hops_shared_top_float_i8(const qmann_net *net, const int8_t *keys, const int8_t *vals, size_t hop_stride,
+                                   uint32_t n_slots, const float *u0, float *u_out, uint32_t k,
+                                   uint32_t *top_slot, float *top_p, uint32_t n_query, void *stream);
+
 /* Packed binary codes for the Hamming forms: sign-magnitude bytes [rows][Dp] -> bit planes
  * uint64 [rows][Dp/64][num_bit] (plane 0 = sign bits, plane i = magnitude bit 7-i; bit b of a word
  * is column 64.g + b).  num_bit in 1..8.  sm_codes 16-byte aligned, planes 8-byte aligned (QMANN_EINVAL otherwise). */

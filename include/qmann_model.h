@@ -108,6 +108,17 @@ int qmann_model_forward_words_top(qmann_model *m, const uint16_t *story_words, u
                                   uint32_t max_slots, uint32_t n_query, const uint32_t *answer, uint32_t *pred,
                                   float *cost, uint32_t *match, uint32_t k, uint32_t *top_slot, float *top_p, void *stream);
 
+/* qmann_model_forward_words_top for a QMANN_ATT_FLOAT model: the same arguments and outputs, the rows those of
+ * qmann_hops_top_float_i8 (qmann_batch.h), at every story length qmann_model_forward_words takes for such a model.  pred, cost,
+ * match, qmann_model_last_u and what qmann_model_last_topk ranks are those of qmann_model_forward_words; it can be captured in a
+ * graph as that call can.  What qmann_model_forward_words refuses or answers without work is answered FIRST and as there; then
+ * QMANN_EUNSUPPORTED for a model that is not QMANN_ATT_FLOAT; then QMANN_EINVAL for k = 0, k > QMANN_MAX_TOP_SLOTS, a null
+ * top_slot or top_p.  Such a call launches nothing and leaves every output as it was. */
+int qmann_model_forward_words_top_float(qmann_model *m, const uint16_t *story_words, uint32_t rows_total, uint32_t max_words,
+                                        const uint16_t *question_words, uint32_t max_q_words, const uint32_t *row_off,
+                                        uint32_t max_slots, uint32_t n_query, const uint32_t *answer, uint32_t *pred,
+                                        float *cost, uint32_t *match, uint32_t k, uint32_t *top_slot, float *top_p, void *stream);
+
 /* One story, many questions: story_words [n_rows][max_words] is embedded ONCE (every hop, or one plane when the hops are tied)
  * and all n_query questions attend to it.  Same results as qmann_model_forward_words on n_query copies of the story.
  * The workspace holds n_rows rows of memory, not n_query x n_rows.  Attention mode QMANN_ATT_FIXED only (what
@@ -153,7 +164,7 @@ uint32_t qmann_model_memory_rows(const qmann_model *m);
  * qmann_model_ask_words_top_packed below (its softmax is per slot (V1) or over up to 2 049 bins (V0), a different selection).
  * What qmann_model_ask_words refuses or answers without work is answered FIRST and as there (nothing memorised: QMANN_EINVAL;
  * n_query = 0: QMANN_OK whatever k; null question_words or pred: QMANN_EINVAL); then QMANN_EUNSUPPORTED for a Hamming model
- * and for a QMANN_ATT_FLOAT model (float attention has no attended-slots form), ahead of any launch; then QMANN_EINVAL for k = 0,
+ * and for a QMANN_ATT_FLOAT model (qmann_model_ask_words_top_float below serves those), ahead of any launch; then QMANN_EINVAL for k = 0,
  * k > QMANN_MAX_TOP_SLOTS, a null top_slot or top_p.  A refused call launches nothing and leaves every output as it was. */
 int qmann_model_ask_words_top(qmann_model *m, const uint16_t *question_words, uint32_t max_q_words, uint32_t n_query,
                               const uint32_t *answer, uint32_t *pred, float *cost, uint32_t *match,
@@ -200,11 +211,23 @@ int qmann_model_enable_split_asks_packed(qmann_model *m, size_t scratch_bytes, v
  * never at ask.  qmann_model_ask_words then gives the same pred, cost, match and qmann_model_last_u as
  * qmann_model_forward_words on n_query copies of the story, bit for bit (cost: up to the order of its float atomics), allocates
  * nothing once the question workspace has its size, and can be captured in a graph; qmann_model_last_topk works after it.
- * qmann_model_ask_words_top / _top_packed keep returning QMANN_EUNSUPPORTED for such a model, before anything is launched, and
- * so do qmann_model_forward_shared_words and both qmann_model_enable_split_asks calls.
+ * qmann_model_ask_words_top / _top_packed keep returning QMANN_EUNSUPPORTED for such a model, before anything is launched
+ * (qmann_model_ask_words_top_float below returns its attended slots), and so do qmann_model_forward_shared_words and both qmann_model_enable_split_asks calls.
  * on = 0 forgets a memorised memory and restores the behaviour above exactly.  The call allocates nothing.
  * Any model whose attention mode is not QMANN_ATT_FLOAT: QMANN_EUNSUPPORTED. */
 int qmann_model_enable_float_asks(qmann_model *m, int on);
+
+/* qmann_model_ask_words_top for a QMANN_ATT_FLOAT model with float asks enabled: the same arguments and outputs, the rows those
+ * of qmann_hops_shared_top_float_i8 (qmann_batch.h) on the memory the model holds.  pred, cost, match, qmann_model_last_u and
+ * what qmann_model_last_topk ranks are those of qmann_model_ask_words; nothing is allocated once the question workspace has its
+ * size, so the call can be captured in a graph and replayed.
+ * What qmann_model_ask_words refuses or answers without work is answered FIRST and as there (nothing memorised -- which is all a
+ * float model without qmann_model_enable_float_asks can have --: QMANN_EINVAL; n_query = 0: QMANN_OK whatever k; null
+ * question_words or pred: QMANN_EINVAL); then QMANN_EUNSUPPORTED for a model that is not QMANN_ATT_FLOAT; then QMANN_EINVAL for
+ * k = 0, k > QMANN_MAX_TOP_SLOTS, a null top_slot or top_p.  A refused call launches nothing and leaves every output as it was. */
+int qmann_model_ask_words_top_float(qmann_model *m, const uint16_t *question_words, uint32_t max_q_words, uint32_t n_query,
+                                    const uint32_t *answer, uint32_t *pred, float *cost, uint32_t *match,
+                                    uint32_t k, uint32_t *top_slot, float *top_p, void *stream);
 
 /* Forward from the reference's float bag-of-words pools (dev_m_test / dev_q_test, MemN2N.c:2337-2349):
  *   story [rows_total][dim_input] float, question [n_query][dim_input] float. */

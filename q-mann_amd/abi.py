@@ -162,6 +162,10 @@ _proto("qmann_hops_i8", C.c_int, [C.POINTER(Net), _vp, _vp, C.c_size_t, _vp, C.c
                                   C.POINTER(Taps), C.c_uint32, _vp])
 _proto("qmann_hops_top_i8", C.c_int, [C.POINTER(Net), _vp, _vp, C.c_size_t, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp,
                                       C.c_uint32, _vp])
+_proto("qmann_hops_top_float_i8", C.c_int, [C.POINTER(Net), _vp, _vp, C.c_size_t, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp,
+                                            C.c_uint32, _vp])
+_proto("qmann_hops_shared_top_float_i8", C.c_int, [C.POINTER(Net), _vp, _vp, C.c_size_t, C.c_uint32, _vp, _vp, C.c_uint32, _vp,
+                                                   _vp, C.c_uint32, _vp])
 _proto("qmann_hops_shared_lds_bytes", C.c_size_t, [C.c_uint32, C.c_uint32])
 _proto("qmann_hops_shared_tile", C.c_uint32, [C.c_uint32, C.c_uint32])
 _proto("qmann_hops_shared_i8", C.c_int, [C.POINTER(Net), _vp, _vp, C.c_size_t, C.c_uint32, _vp, _vp,
@@ -236,6 +240,8 @@ _proto("qmann_model_forward_words", C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, 
                                               C.c_uint32, _vp, _vp, _vp, _vp, _vp])
 _proto("qmann_model_forward_words_top", C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _vp, C.c_uint32, _vp, C.c_uint32,
                                                   C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp])
+_proto("qmann_model_forward_words_top_float", C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _vp, C.c_uint32, _vp, C.c_uint32,
+                                                        C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp])
 _proto("qmann_model_forward_shared_words", C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _vp, C.c_uint32, C.c_uint32,
                                                      _vp, _vp, _vp, _vp, _vp])
 _proto("qmann_model_memorize_words", C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _vp])
@@ -243,6 +249,8 @@ _proto("qmann_model_ask_words", C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _vp,
 _proto("qmann_model_ask_words_top", C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp])
 _proto("qmann_model_ask_words_top_packed", C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp,
                                                      _vp])
+_proto("qmann_model_ask_words_top_float", C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp,
+                                                    _vp])
 _proto("qmann_model_memory_rows", C.c_uint32, [_vp])
 _proto("qmann_model_forward_bow", C.c_int, [_vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, _vp])
 _proto("qmann_model_enable_split_asks", C.c_int, [_vp, C.c_size_t, _vp])

@@ -358,10 +358,13 @@ int qm_hops_i8(const qmann_net *net, const int8_t *keys, const int8_t *vals, siz
     if (qm_too_many_queries(n_query)) return QMANN_ERANGE;
 
     if (net->attention_mode == QMANN_ATT_FLOAT) {
-        // (attended slots: float attention is not served -- behind the one refusal the float launcher has of its own)
+        if (hints.top_float) return qmann_hops_top_float_impl(a, net->dim_emb_pad, max_slots, hints.top_k, hints.top_slot, hints.top_p, n_query, stream);
+        // (attended slots through qmann_hops_top_i8: float attention is not served -- behind the one refusal the float launcher
+        // has of its own; qmann_hops_top_float_i8 is the call that serves it)
         if (hints.top_on) return (size_t)kOffScores + (((size_t)max_slots * 4 + 15) & ~(size_t)15) > 160 * 1024 - 1024 ? QMANN_ERANGE : QMANN_EUNSUPPORTED;
         return qmann_hops_float_impl(a, net->dim_emb_pad, max_slots, n_query, stream);
     }
+    if (hints.top_float) return QMANN_EUNSUPPORTED;       // (qmann_hops_top_float_i8: float attention only)
     if (hints.top_on && !story_top_args_ok(hints.top_k, hints.top_slot, hints.top_p)) return QMANN_EINVAL;     // behind every refusal of the base call
 
     hipStream_t st = (hipStream_t)stream;
@@ -403,5 +406,16 @@ extern "C" int qmann_hops_top_i8(const qmann_net *net, const int8_t *keys, const
 {
     QmHopHints hints;
     hints.top_on = true; hints.top_k = k; hints.top_slot = top_slot; hints.top_p = top_p;
+    return qm_hops_i8(net, keys, vals, hop_stride, row_off, max_slots, u0, u_out, nullptr, n_query, stream, hints);
+}
+
+// qmann_hops_i8 (float attention) without taps plus the attended slots of every hop: one kernel on `stream`
+// (batch_hops_top_float.hip, hops_attended_float.h)
+extern "C" int qmann_hops_top_float_i8(const qmann_net *net, const int8_t *keys, const int8_t *vals, size_t hop_stride, const uint32_t *row_off,
+                                       uint32_t max_slots, const float *u0, float *u_out, uint32_t k, uint32_t *top_slot, float *top_p,
+                                       uint32_t n_query, void *stream)
+{
+    QmHopHints hints;
+    hints.top_on = hints.top_float = true; hints.top_k = k; hints.top_slot = top_slot; hints.top_p = top_p;
     return qm_hops_i8(net, keys, vals, hop_stride, row_off, max_slots, u0, u_out, nullptr, n_query, stream, hints);
 }

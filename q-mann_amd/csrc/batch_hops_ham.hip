@@ -304,6 +304,7 @@ int ham_prepare(HopArgs &a, size_t &lds, const qmann_net *net, const void *keys,
 int ham_top_check(const QmHopHints &hints, uint32_t max_slots)
 {
     if (!hints.top_on) return QMANN_OK;
+    if (hints.top_float) return QMANN_EUNSUPPORTED;             // (qmann_hops_top_float_i8: float attention only)
     if (max_slots > (uint32_t)kWave) return QMANN_EUNSUPPORTED;
     return story_top_args_ok(hints.top_k, hints.top_slot, hints.top_p) ? QMANN_OK : QMANN_EINVAL;
 }

@@ -1,40 +1,42 @@
-// batch_hops_shared_float.hip -- qmann_hops_shared_float_i8: float attention (ATTENTION_MODE 1) when every query reads the SAME
-// memory.  To batch_hops_float.hip what batch_hops_shared.hip is to batch_hops.hip.
+// batch_hops_top_float.hip -- attended slots for float attention (ATTENTION_MODE 1): qmann_hops_top_float_i8 (every query its own
+// memory) and qmann_hops_shared_top_float_i8 (one memory for all queries).  The hop kernels of batch_hops_float.hip and
+// batch_hops_shared_float.hip with the selection of hops_attended_float.h behind the softmax of each query's hop: the k rows
+// a hop weighted most leave the kernel, and no [n_hop][rows] probability array is written.
 //
-// k_hops_float gives a workgroup one query and streams that query's private key AND value planes from HBM (p is not quantised:
-// every value row counts).  Here both planes are one for all queries and stay in L2, so the hop is vector-issue work, and what
-// depends on the memory alone is done once for a tile of QT queries.  One 256-thread workgroup owns QT queries and per hop
-//
-//   1. scans the key plane ONCE for its tile: per loaded dword the sign mask and the magnitudes are taken once, then one select and
-//      one v_dot4 per query against that query's constants (the scores are the exact integers of k_hops_float's dot_lane_sum);
-//   2. runs the softmax per query on the query's own slice of LDS (hops_float_common.h::float_softmax_slots: k_hops_float's stage,
-//      same thread-to-slot mapping, same reductions, same quotient);
-//   3. reads the value plane ONCE for its tile: each loaded dword becomes four floats once (6 word operations + 4 converts), then
-//      one FMA per byte and query.  Every query's additions run in k_hops_float's order -- the same rows on the same lanes in the
-//      same tiles, the same __shfl_xor fold, the same per-wavefront partials summed in wavefront order -- which makes o, and with
-//      it everything behind it, bit-equal to the per-story kernel's;
-//   4. linear map and hop update per query (hops_common.h::linmap_update).
-//
-// A last tile with fewer than QT queries scans and reads out with a live query's constants and weights in the spare places and
-// drops their sums: nothing is stored for them.
+// ONE kernel text serves both calls, in a unit of its own.  A TOP switch on k_hops_float or k_hops_shared_float -- even as a thin
+// kernel around one shared body -- changes the plain builds' device code (register allocation from the first kernarg load on:
+// tools/device_asm_equal.sh), and those are the measured kernels.  So this is k_hops_shared_float's text (the tile of QT queries,
+// the key-only and memory-only work done once per tile, every query's float additions in k_hops_float's order) with AttTop<true>
+// as its last argument, and its STORY build is the per-story kernel: one query per workgroup on rows row_off[q] ..
+// row_off[q + 1] of private planes, the length cut to max_slots, an empty story allowed, the planes streamed past the caches as
+// k_hops_float streams them.  k_hops_shared_float promises k_hops_float's bits under every tile, so both builds give the
+// `probs` tap's floats and the base calls' u_out.  Keep the three texts in step.  No taps are written.
+#include "hops_attended_float.h"
 #include "hops_float_common.h"
 #include "hops_host.h"
 
 namespace {
 
-constexpr size_t kSharedFloatLdsLimit = 160 * 1024 - 1024;     // as qmann_hops_i8: a little static LDS is used besides
+constexpr size_t kTopFloatLdsLimit = 160 * 1024 - 1024;       // as the base calls: a little static LDS is used besides
 
-// per_q: bytes of LDS per query (qmann_hops_shared_float_lds_bytes(n_slots, 1)); a.max_slots = n_slots >= 1
-template <int LPR, int QT>
+// STORY: QT = 1, per_q unused.  Shared: per_q = bytes of LDS per query, a.max_slots = n_slots >= 1, a.row_off unused
+template <int LPR, int QT, bool STORY>
 __global__ void __launch_bounds__(kBlock)
-k_hops_shared_float(const HopArgs a, const uint32_t n_query, const uint32_t per_q)
+k_hops_top_float(const HopArgs a, const uint32_t n_query, const uint32_t per_q, const AttTop<true> tp)
 {
+    static_assert(!STORY || QT == 1, "a story is one query's");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr uint32_t Dp = LPR * 16;
     const uint32_t tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
     const uint32_t q0 = blockIdx.x * QT;
     const uint32_t nq = n_query - q0 < (uint32_t)QT ? n_query - q0 : (uint32_t)QT;     // queries of this tile (the last may be short)
-    const uint32_t S = a.max_slots, D = a.D;
+    uint32_t r0 = 0, S = a.max_slots;
+    if constexpr (STORY) {
+        r0 = a.row_off[q0];
+        const uint32_t S_in = a.row_off[q0 + 1] - r0;
+        S = S_in < a.max_slots ? S_in : a.max_slots;              // never index LDS past what the launch reserved
+    }
+    const uint32_t D = a.D;
     // the slice of place t: a spare place of a short tile reads the last live query's
     auto slice = [&](uint32_t t) { return smem + (t < nq ? t : nq - 1) * per_q; };
 
@@ -54,14 +56,18 @@ k_hops_shared_float(const HopArgs a, const uint32_t n_query, const uint32_t per_
 
         // the key scan: one pass over the plane for the whole tile
         const float scale = qm_scale_down(1.0f, fw.frac + fsrc.frac);
-        {
+        if (S > 0) {
             FloatDotConst c[QT];
 #pragma unroll
             for (int t = 0; t < QT; t++) make_float_dot_const(c[t], FloatQueryLds(slice((uint32_t)t)).kuq, (lane % LPR) * 16);
-            const uint8_t *kb = (const uint8_t *)a.keys + (size_t)h * a.hop_stride;
+            const uint8_t *kb = (const uint8_t *)a.keys + (size_t)h * a.hop_stride + (size_t)r0 * Dp;
             auto retire = [&](uint32_t t, uint32_t r, int v) { FloatQueryLds(smem + t * per_q).sc[r] = v; };
             if (S >= (kWave / LPR) * 4) {
-                scan_rows_shared_float<LPR, 4, QT>(kb, S, c, nq, retire, lane, wave);
+                if constexpr (STORY)
+                    scan_rows<LPR, 4, true, kWaves>(kb, S, [&](const i32x4 x) { return float_dot_lane_sum(x, c[0]); },
+                                                    [&](uint32_t r, int v) { retire(0u, r, v); }, lane, wave);
+                else
+                    scan_rows_shared_float<LPR, 4, QT>(kb, S, c, nq, retire, lane, wave);
             } else {                                                 // below one tile of rows: right, not fast
 #pragma unroll
                 for (int t = 0; t < QT; t++)
@@ -72,12 +78,20 @@ k_hops_shared_float(const HopArgs a, const uint32_t n_query, const uint32_t per_
         }
         __syncthreads();
 
-        // softmax per query on its slice; p replaces the score in place
-        for (uint32_t t = 0; t < nq; t++) {
-            const FloatQueryLds L(slice(t));
-            float_softmax_slots(a, h, S, scale, ((size_t)h * n_query + q0 + t) * S, L.sc, L.red, tid, lane, wave);
+        // softmax per query on its slice; p replaces the score in place (no taps: the offset is unused)
+        if (S > 0) {
+            for (uint32_t t = 0; t < nq; t++) {
+                const FloatQueryLds L(slice(t));
+                float_softmax_slots(a, h, S, scale, 0, L.sc, L.red, tid, lane, wave);
+            }
         }
         __syncthreads();
+
+        // the attended slots of every live query, each from its own slice (spare places: nothing runs, nothing is stored)
+        for (uint32_t t = 0; t < nq; t++) {
+            const FloatQueryLds L(smem + t * per_q);
+            attended_select_float(tp, (size_t)(q0 + t) * a.n_hop + h, S, (const float *)L.sc, L.red, tid, lane, wave);
+        }
 
         // dense float read-out for the whole tile: k_hops_float's value tiles (lane (sub, chunk) owns 16 columns of every
         // (64 / LPR)-th row; UN loads per lane, the next tile in flight), each loaded dword converted once
@@ -95,7 +109,7 @@ k_hops_shared_float(const HopArgs a, const uint32_t n_query, const uint32_t per_
 #pragma unroll
                 for (int i = 0; i < 16; i++) acc[t][i] = 0.0f;
             }
-            const uint8_t *vb = (const uint8_t *)a.vals + (size_t)h * a.hop_stride + chunk * 16;
+            const uint8_t *vb = (const uint8_t *)a.vals + (size_t)h * a.hop_stride + (size_t)r0 * Dp + chunk * 16;
             // acc[t][i] += (p_t . 2^-frac) . code; `live`: false for the rows a moved-back tile repeats, which add zero
             auto accumulate = [&](const i32x4 x, uint32_t r, bool live) {
                 float ps[QT];
@@ -120,7 +134,7 @@ k_hops_shared_float(const HopArgs a, const uint32_t n_query, const uint32_t per_
                 auto issue = [&](i32x4 (&x)[UN], uint32_t base) {
                     const uint8_t *pp = vb + (size_t)(tile_start(base) + sub) * Dp;
 #pragma unroll
-                    for (int j = 0; j < UN; j++) x[j] = *(const i32x4 *)(pp + (size_t)j * RPW * Dp);     // plain: the plane is to stay in L2
+                    for (int j = 0; j < UN; j++) x[j] = load16<STORY>(pp + (size_t)j * RPW * Dp);     // a shared plane is to stay in L2
                 };
                 auto consume = [&](const i32x4 (&x)[UN], uint32_t base) {
                     const uint32_t start = tile_start(base);
@@ -188,62 +202,53 @@ k_hops_shared_float(const HopArgs a, const uint32_t n_query, const uint32_t per_
     }
 }
 
-// Queries per workgroup.  What LDS allows is the frame (a float per slot and query: 2 at 10 000 slots, 8 up to 2 752); inside it
-// the choice is by measurement (tools/shared_float_ab.py, 4 096 queries x 3 hops, five interleaved rounds; every round is in
-// DESIGN.md section 5, "Measured, shared plane, float"), and the measurement says ONE query per workgroup at all three shapes:
-// 10 000 x 128: 2.54 ms (2: 3.47); 1 000 x 60: 0.229 ms (2: 0.240, 4: 0.370, 8: 0.356); 200 x 60: 0.131 ms (2: 0.150, 4: 0.231,
-// 8: 0.221) -- against 4.81 / 0.292 / 0.149 ms for qmann_hops_i8 on copies.  A larger tile does less vector work per query but
-// leaves fewer wavefronts on a SIMD (182 registers from two queries on, and at 10 000 slots two slices fill a CU's LDS), and the
-// L2 latency of two tiles in flight is then no longer covered.  Between and beyond those shapes nothing is measured: the choice is
-// 1 everywhere.  QMANN_SHARED_QT (1, 2, 4, 8) forces a tile size that fits, for that measurement and for the tests.
-uint32_t choose_float_qt(uint32_t n_slots, uint32_t n_query)
-{
-    (void)n_query;
-    uint32_t fit = 8;
-    while (fit > 1 && qmann_hops_shared_float_lds_bytes(n_slots, fit) > kSharedFloatLdsLimit) fit >>= 1;
-    const uint32_t forced = qm_tuning().shared_qt;
-    if (forced) return forced < fit ? forced : fit;
-    return 1;
-}
-
 }  // namespace
+
+// the per-story call's last steps, on the HopArgs that qm_hops_i8 has checked and filled (taps: none)
+extern "C" int qmann_hops_top_float_impl(const HopArgs &a, uint32_t Dp, uint32_t max_slots, uint32_t k, uint32_t *top_slot, float *top_p,
+                                         uint32_t n_query, void *stream)
+{
+    QmBatched qm_scope;
+    const size_t lds = (size_t)kOffScores + (((size_t)max_slots * 4 + 15) & ~(size_t)15);
+    if (lds > kTopFloatLdsLimit) return QMANN_ERANGE;                      // (the float launcher's own refusal)
+    if (!att_top_args_ok(k, top_slot, top_p)) return QMANN_EINVAL;         // behind every refusal of the base call
+    const AttTop<true> tp{top_slot, top_p, k};
+    qm_dispatch<4, 8, 16>(Dp / 16, [&](auto lpr) {
+        qm_launch(k_hops_top_float<decltype(lpr)::value, 1, true>, n_query, dim3(kBlock), lds, (hipStream_t)stream, a, n_query, 0u, tp);
+    });
+    QM_LAUNCH_CHECK();
+    return qm_scope.rc();
+}
 
 extern "C" {
 
-size_t qmann_hops_shared_float_lds_bytes(uint32_t n_slots, uint32_t queries_per_group)
-{
-    return (size_t)queries_per_group * (qmann_hops_lds_bytes(0) + (((size_t)n_slots * 4 + 15) & ~(size_t)15));
-}
-
-uint32_t qmann_hops_shared_float_tile(uint32_t n_slots, uint32_t n_query)
-{
-    if (n_slots == 0 || n_query == 0 || qmann_hops_shared_float_lds_bytes(n_slots, 1) > kSharedFloatLdsLimit) return 0;
-    return choose_float_qt(n_slots, n_query);
-}
-
-int qmann_hops_shared_float_i8(const qmann_net *net, const int8_t *keys, const int8_t *vals, size_t hop_stride, uint32_t n_slots,
-                               const float *u0, float *u_out, const qmann_taps *taps, uint32_t n_query, void *stream)
+int qmann_hops_shared_top_float_i8(const qmann_net *net, const int8_t *keys, const int8_t *vals, size_t hop_stride, uint32_t n_slots,
+                                   const float *u0, float *u_out, uint32_t k, uint32_t *top_slot, float *top_p, uint32_t n_query,
+                                   void *stream)
 {
     QmBatched qm_scope;
-    static_assert(kOffScores % 16 == 0, "a query's slice starts 16-byte aligned");
+    // qmann_hops_shared_float_i8's refusals, in its order
     static const uint32_t no_row_off = 0;                     // this call has no row_off: the shared checks want a non-null one
     if (const int rc = check_hop_call(net, keys, vals, &no_row_off, u0, u_out)) return rc;
     HopArgs a;
-    if (const int rc = fill_hop_args(a, net, keys, vals, hop_stride, hop_stride, &no_row_off, u0, u_out, taps)) return rc;
+    if (const int rc = fill_hop_args(a, net, keys, vals, hop_stride, hop_stride, &no_row_off, u0, u_out, nullptr)) return rc;
     if (net->attention_mode != QMANN_ATT_FLOAT) return QMANN_EUNSUPPORTED;
     if (n_slots == 0) return QMANN_EINVAL;
     a.row_off = nullptr;
     a.max_slots = a.rows_total = n_slots;
-    if (qmann_hops_shared_float_lds_bytes(n_slots, 1) > kSharedFloatLdsLimit) return QMANN_ERANGE;
+    if (qmann_hops_shared_float_lds_bytes(n_slots, 1) > kTopFloatLdsLimit) return QMANN_ERANGE;
     if (n_query == 0) return QMANN_OK;
     if (qm_too_many_queries(n_query)) return QMANN_ERANGE;
+    if (!att_top_args_ok(k, top_slot, top_p)) return QMANN_EINVAL;         // behind every refusal of the base call
 
-    const uint32_t qt = choose_float_qt(n_slots, n_query), per_q = (uint32_t)qmann_hops_shared_float_lds_bytes(n_slots, 1);
+    const AttTop<true> tp{top_slot, top_p, k};
+    const uint32_t qt = qmann_hops_shared_float_tile(n_slots, n_query);    // the base call's tile (QMANN_SHARED_QT forces one)
+    const uint32_t per_q = (uint32_t)qmann_hops_shared_float_lds_bytes(n_slots, 1);
     qm_dispatch<4, 8, 16>(net->dim_emb_pad / 16, [&](auto lpr) {
         qm_dispatch<1, 2, 4, 8>(qt, [&](auto t) {
             constexpr int LPR = decltype(lpr)::value, QT = decltype(t)::value;
-            qm_launch(k_hops_shared_float<LPR, QT>, qm_cdiv(n_query, qt), dim3(kBlock), (size_t)qt * per_q, (hipStream_t)stream, a,
-                      n_query, per_q);
+            qm_launch(k_hops_top_float<LPR, QT, false>, qm_cdiv(n_query, qt), dim3(kBlock), (size_t)qt * per_q, (hipStream_t)stream, a,
+                      n_query, per_q, tp);
         });
     });
     QM_LAUNCH_CHECK();

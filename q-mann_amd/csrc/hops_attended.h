@@ -20,18 +20,9 @@
 // LDS: the query's own live_row (entries), live_kp (class per bin), misc[2], misc[4..11] and red, all free behind finish_hop.
 #pragma once
 #include "hops_shared.h"
+#include "hops_att_top.h"
 
 namespace {
-
-// launch argument of the kernels' TOP builds; the other builds take an EMPTY one and keep their device code
-template <bool TOP> struct AttTop {};
-template <> struct AttTop<true> {
-    uint32_t *slot;          // [n_query][n_hop][k]
-    float *p;                // [n_query][n_hop][k]
-    uint32_t k;              // 1 .. QMANN_MAX_TOP_SLOTS
-};
-
-__device__ __forceinline__ float att_key(float p) { return p == p ? p : -INFINITY; }
 
 // Called by the whole workgroup (kBlock threads) behind finish_hop; `row` = q . n_hop + h.  Ends with a barrier.
 __device__ __forceinline__ void attended_select(const AttTop<true> &tp, size_t row, uint32_t S, const uint32_t *hist, const float *ptab,
@@ -133,12 +124,6 @@ __device__ __forceinline__ void attended_select(const AttTop<true> &tp, size_t r
         tp.p[row * k + rank] = p;
     }
     __syncthreads();
-}
-
-// what both top calls refuse beyond their base calls
-inline bool att_top_args_ok(uint32_t k, const uint32_t *top_slot, const float *top_p)
-{
-    return k >= 1 && k <= (uint32_t)QMANN_MAX_TOP_SLOTS && top_slot && top_p;
 }
 
 }  // namespace

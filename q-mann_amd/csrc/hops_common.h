@@ -37,6 +37,10 @@ using qmann::HopArgs;
 
 // float attention on the HopArgs that qmann_hops_i8 has checked and filled (batch_hops_float.hip)
 extern "C" int qmann_hops_float_impl(const HopArgs &a, uint32_t Dp, uint32_t max_slots, uint32_t n_query, void *stream);
+// ... and with each hop's attended slots, top_slot / top_p [n_query][n_hop][k]; checks its LDS bound, then k and the two
+// pointers (batch_hops_top_float.hip)
+extern "C" int qmann_hops_top_float_impl(const HopArgs &a, uint32_t Dp, uint32_t max_slots, uint32_t k, uint32_t *top_slot, float *top_p,
+                                         uint32_t n_query, void *stream);
 
 namespace {
 

@@ -102,4 +102,79 @@ __device__ __forceinline__ void float_softmax_slots(const HopArgs &a, uint32_t h
     }
 }
 
+// one query's slice of the workgroup's LDS: k_hops_float's use of hops_common.h's carve-up
+struct FloatQueryLds {
+    float *u_f, *o_f, *part;
+    short *ku;
+    int8_t *kuq;              // integer codes of u on its own grid (reuses the histogram area)
+    double *red;
+    int32_t *sc;              // scores, then p (float, in place)
+    __device__ __forceinline__ explicit FloatQueryLds(unsigned char *b)
+        : u_f((float *)(b + kOffU)), o_f((float *)(b + kOffO)), part((float *)(b + kOffHist + 1024)), ku((short *)(b + kOffKu)),
+          kuq((int8_t *)(b + kOffHist)), red((double *)(b + kOffRed)), sc((int32_t *)(b + kOffScores)) {}
+};
+static_assert(kOffHist + 1024 + kWaves * 256 * 4 <= kOffU, "partial sums must fit the histogram + p-table area");
+
+// hops_common.h::scan_rows<LPR, UN, false, kWaves> for a tile of QT queries on one plane: the same tiles, the same two in flight,
+// the same moved-back last tile.  retire(t, r, v): row r of query t has sum v; places t >= nq are computed and dropped.
+// Needs S >= one tile of rows.
+template <int LPR, int UN, int QT, typename Retire>
+__device__ __forceinline__ void scan_rows_shared_float(const uint8_t *__restrict__ kb, uint32_t S, const FloatDotConst (&c)[QT], uint32_t nq,
+                                                       Retire retire, uint32_t lane, uint32_t wave)
+{
+    constexpr uint32_t RPW = kWave / LPR, TILE = RPW * UN, Dp = LPR * 16, STEP = kWaves * TILE;
+    const uint32_t sub = lane / LPR, chunk = lane % LPR;
+    const uint32_t n_tiles = (S + TILE - 1) / TILE;
+    const uint8_t *lane_base = kb + chunk * 16;
+    auto tile_start = [&](uint32_t base) { return base + TILE <= S ? base : S - TILE; };
+    auto issue = [&](i32x4 (&x)[UN], uint32_t base) {
+        const uint8_t *p = lane_base + (size_t)(tile_start(base) + sub) * Dp;
+#pragma unroll
+        for (int j = 0; j < UN; j++) x[j] = load16<false>(p + (size_t)j * RPW * Dp);
+    };
+    auto reduce = [&](const i32x4 (&x)[UN], uint32_t base) {
+        int s[QT][UN];
+#pragma unroll
+        for (int j = 0; j < UN; j++) {
+            uint32_t neg[4], mag[4];
+#pragma unroll
+            for (int d = 0; d < 4; d++) float_key_split((uint32_t)x[j][d], neg[d], mag[d]);      // key-only work: once per tile of queries
+#pragma unroll
+            for (int t = 0; t < QT; t++) {
+                int acc = 0;
+#pragma unroll
+                for (int d = 0; d < 4; d++) acc = float_dot4(neg[d], mag[d], c[t].up[d], c[t].un[d], acc);
+                s[t][j] = row_lanes_sum<LPR>(acc);
+            }
+        }
+        const uint32_t start = tile_start(base);
+#pragma unroll
+        for (int t = 0; t < QT; t++) {
+            if ((uint32_t)t >= nq) break;                          // (workgroup-uniform)
+#pragma unroll
+            for (int j0 = 0; j0 < UN; j0 += LPR) {                 // lane (sub, chunk) retires row j0 + chunk, as scan_rows does
+                int v = s[t][j0];
+#pragma unroll
+                for (int k = 1; k < LPR && j0 + k < UN; k++) v = (chunk == (uint32_t)k) ? s[t][j0 + k] : v;
+                const uint32_t j = j0 + chunk;
+                const uint32_t r = start + j * RPW + sub;
+                if (j < (uint32_t)UN && r >= base) retire((uint32_t)t, r, v);
+            }
+        }
+    };
+
+    if (wave >= n_tiles) return;
+    i32x4 xa[UN], xb[UN];
+    uint32_t base = wave * TILE;
+    issue(xa, base);
+    for (uint32_t t = wave; t < n_tiles; t += 2 * kWaves) {
+        issue(xb, base + STEP);
+        reduce(xa, base);
+        if (t + kWaves >= n_tiles) break;
+        issue(xa, base + 2 * STEP);
+        reduce(xb, base + STEP);
+        base += 2 * STEP;
+    }
+}
+
 }  // namespace

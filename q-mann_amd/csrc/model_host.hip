@@ -341,7 +341,7 @@ int hops_and_answer(qmann_model *m, uint32_t rows_total, const uint32_t *row_off
 {
     const size_t hop_stride = m->tied ? 0 : (size_t)rows_total * m->Dp;
     QmHopHints hints{rows_total, split_ws};          // (a tied model passes hop_stride = 0: the hop kernels still learn the plane's size)
-    if (top) { hints.top_on = true; hints.top_k = top->top_k; hints.top_slot = top->top_slot; hints.top_p = top->top_p; }
+    if (top) { hints.top_on = true; hints.top_float = top->top_float; hints.top_k = top->top_k; hints.top_slot = top->top_slot; hints.top_p = top->top_p; }
     int rc;
     if (use_planes(m, max_slots)) {
         const size_t key_hop_stride = m->tied ? 0 : (size_t)rows_total * (m->Dp / 64) * m->net.num_bit * 8;
@@ -540,7 +540,8 @@ int qmann_model_net(const qmann_model *m, qmann_net *net, const float **w_ans)
     return QMANN_OK;
 }
 
-// qmann_model_forward_words (top null) and qmann_model_forward_words_top (the top fields of `top` as the caller gave them)
+// qmann_model_forward_words (top null), qmann_model_forward_words_top and qmann_model_forward_words_top_float (the top fields of
+// `top` as the caller gave them; top_float: the float form)
 static int forward_words_impl(qmann_model *m, const uint16_t *story_words, uint32_t rows_total, uint32_t max_words,
                               const uint16_t *question_words, uint32_t max_q_words, const uint32_t *row_off,
                               uint32_t max_slots, uint32_t n_query, const uint32_t *answer, uint32_t *pred,
@@ -554,8 +555,10 @@ static int forward_words_impl(qmann_model *m, const uint16_t *story_words, uint3
     if (top) {
         // what qmann_hops_top_i8 would refuse behind its base call, said here ahead of any launch: the modes and lengths it does
         // not serve, then its own arguments.  (Beyond 64 slots only fixed-point models pass: the packed-plane route is never taken.)
+        // qmann_hops_top_float_i8 serves float attention at every length its base call does, and nothing else.
         const uint32_t am = m->net.attention_mode;
-        if (am == QMANN_ATT_FLOAT || (am != QMANN_ATT_FIXED && max_slots > 64)) return QMANN_EUNSUPPORTED;
+        if (top->top_float ? am != QMANN_ATT_FLOAT : am == QMANN_ATT_FLOAT) return QMANN_EUNSUPPORTED;
+        if (!top->top_float && am != QMANN_ATT_FIXED && max_slots > 64) return QMANN_EUNSUPPORTED;
         if (top->top_k < 1 || top->top_k > (uint32_t)QMANN_MAX_TOP_SLOTS || !top->top_slot || !top->top_p) return QMANN_EINVAL;
     }
     DeviceScope on(m->device);
@@ -589,6 +592,17 @@ int qmann_model_forward_words_top(qmann_model *m, const uint16_t *story_words, u
 {
     QmHopHints top;
     top.top_on = true; top.top_k = k; top.top_slot = top_slot; top.top_p = top_p;
+    return forward_words_impl(m, story_words, rows_total, max_words, question_words, max_q_words, row_off, max_slots, n_query,
+                              answer, pred, cost, match, stream, &top);
+}
+
+int qmann_model_forward_words_top_float(qmann_model *m, const uint16_t *story_words, uint32_t rows_total, uint32_t max_words,
+                                        const uint16_t *question_words, uint32_t max_q_words, const uint32_t *row_off,
+                                        uint32_t max_slots, uint32_t n_query, const uint32_t *answer, uint32_t *pred,
+                                        float *cost, uint32_t *match, uint32_t k, uint32_t *top_slot, float *top_p, void *stream)
+{
+    QmHopHints top;
+    top.top_on = top.top_float = true; top.top_k = k; top.top_slot = top_slot; top.top_p = top_p;
     return forward_words_impl(m, story_words, rows_total, max_words, question_words, max_q_words, row_off, max_slots, n_query,
                               answer, pred, cost, match, stream, &top);
 }
@@ -658,9 +672,10 @@ int qmann_model_memorize_words(qmann_model *m, const uint16_t *story_words, uint
     return QMANN_OK;
 }
 
-// qmann_model_ask_words (kAskPlain), qmann_model_ask_words_top (kAskTop: fixed-point models) and
-// qmann_model_ask_words_top_packed (kAskTopPacked: Hamming V0 / V1 models); k, top_slot, top_p as the top calls take them
-enum AskTop { kAskPlain, kAskTop, kAskTopPacked };
+// qmann_model_ask_words (kAskPlain), qmann_model_ask_words_top (kAskTop: fixed-point models),
+// qmann_model_ask_words_top_packed (kAskTopPacked: Hamming V0 / V1 models) and qmann_model_ask_words_top_float (kAskTopFloat:
+// float models with float asks enabled); k, top_slot, top_p as the top calls take them
+enum AskTop { kAskPlain, kAskTop, kAskTopPacked, kAskTopFloat };
 static int ask_words_impl(qmann_model *m, const uint16_t *question_words, uint32_t max_q_words, uint32_t n_query,
                           const uint32_t *answer, uint32_t *pred, float *cost, uint32_t *match, AskTop top, uint32_t k,
                           uint32_t *top_slot, float *top_p, void *stream)
@@ -672,8 +687,9 @@ static int ask_words_impl(qmann_model *m, const uint16_t *question_words, uint32
     m->last_n_query = 0;                                // (set again where this call succeeds)
     if (!question_words || !pred) return QMANN_EINVAL;
     if (top) {                                          // behind the base call's refusals, and here: an ask must not fail behind its embedding
-        if (m->net.attention_mode == QMANN_ATT_FLOAT) return QMANN_EUNSUPPORTED;          // (float attention has no attended-slots form)
-        if (packed_mode(m->net) != (top == kAskTopPacked)) return QMANN_EUNSUPPORTED;     // each form serves its own models
+        // (float attention has a form of its own, qmann_hops_shared_top_float_i8: that one serves float models only, the other two none)
+        if ((m->net.attention_mode == QMANN_ATT_FLOAT) != (top == kAskTopFloat)) return QMANN_EUNSUPPORTED;
+        if (top != kAskTopFloat && packed_mode(m->net) != (top == kAskTopPacked)) return QMANN_EUNSUPPORTED;     // each form serves its own models
         if (k == 0 || k > QMANN_MAX_TOP_SLOTS || !top_slot || !top_p) return QMANN_EINVAL;
     }
     DeviceScope on(m->device);
@@ -704,7 +720,9 @@ static int ask_words_impl(qmann_model *m, const uint16_t *question_words, uint32
                         : qmann_hops_shared_split_i8(&m->net, m->mem_keys, m->mem_vals, plane, S, u0, u, nullptr, nq, 0, m->split_ws,
                                                      m->split_bytes, stream);
         }
-    } else if (m->net.attention_mode == QMANN_ATT_FLOAT)
+    } else if (top == kAskTopFloat)
+        rc = qmann_hops_shared_top_float_i8(&m->net, m->mem_keys, m->mem_vals, plane, S, m->u0, m->u, k, top_slot, top_p, n_query, stream);
+    else if (m->net.attention_mode == QMANN_ATT_FLOAT)
         rc = qmann_hops_shared_float_i8(&m->net, m->mem_keys, m->mem_vals, plane, S, m->u0, m->u, nullptr, n_query, stream);
     else if (packed && top)
         rc = qmann_hops_shared_top_packed(&m->net, m->mem_planes, key_plane, m->mem_vals, plane, S, m->u0, m->u, k, top_slot, top_p,
@@ -740,6 +758,13 @@ int qmann_model_ask_words_top_packed(qmann_model *m, const uint16_t *question_wo
                                      uint32_t *top_slot, float *top_p, void *stream)
 {
     return ask_words_impl(m, question_words, max_q_words, n_query, answer, pred, cost, match, kAskTopPacked, k, top_slot, top_p, stream);
+}
+
+int qmann_model_ask_words_top_float(qmann_model *m, const uint16_t *question_words, uint32_t max_q_words, uint32_t n_query,
+                                    const uint32_t *answer, uint32_t *pred, float *cost, uint32_t *match, uint32_t k,
+                                    uint32_t *top_slot, float *top_p, void *stream)
+{
+    return ask_words_impl(m, question_words, max_q_words, n_query, answer, pred, cost, match, kAskTopFloat, k, top_slot, top_p, stream);
 }
 
 uint32_t qmann_model_memory_rows(const qmann_model *m) { return m ? m->mem_rows : 0u; }

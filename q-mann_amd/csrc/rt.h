@@ -109,6 +109,9 @@ struct QmHopHints {
     // qmann_hops_top_i8: the call also returns each hop's attended slots -- top_slot / top_p [n_query][n_hop][top_k], unchecked
     // until the base call's own refusals are through (the entry points check them last); top_on = false: a plain call
     bool top_on = false;
+    // qmann_hops_top_float_i8: the attended slots of float attention -- every other mode answers QMANN_EUNSUPPORTED where it would
+    // check top_k / top_slot / top_p, and float attention serves the call instead of refusing it (needs top_on)
+    bool top_float = false;
     uint32_t top_k = 0;
     uint32_t *top_slot = nullptr;
     float *top_p = nullptr;

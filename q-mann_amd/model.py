@@ -286,6 +286,36 @@ class QNet:
                   "qmann_hops_top_i8")
         return u_out, top_slot, top_p
 
+    def hops_top_float(self, keys, vals, row_off, max_slots, u0, k):
+        """qmann_hops_top_float_i8: hops_top for float attention (attention_mode 1), at every story length hops takes in that
+        mode: (u_out, top_slot int32 [B][H][k], top_p float32 [B][H][k]); arguments and padding as hops_top."""
+        B = u0.shape[0]
+        rows = keys.shape[1]
+        assert keys.shape in ((self.H, rows, self.Dp), (1, rows, self.Dp)) and vals.shape == keys.shape
+        assert keys.is_contiguous() and vals.is_contiguous()
+        u_out = torch.empty_like(u0)
+        top_slot, top_p = _top_out(self.dev, B, self.H, k)
+        hop_stride = rows * self.Dp if keys.shape[0] == self.H else 0             # one plane for several hops: tied
+        abi.check(abi.lib.qmann_hops_top_float_i8(C.byref(self.net), _ptr(keys), _ptr(vals), hop_stride, _ptr(row_off), max_slots,
+                                                  _ptr(u0), _ptr(u_out), k, _ptr(top_slot), _ptr(top_p), B, self._s()),
+                  "qmann_hops_top_float_i8")
+        return u_out, top_slot, top_p
+
+    def hops_shared_top_float(self, keys, vals, n_slots, u0, k):
+        """qmann_hops_shared_top_float_i8: hops_shared_float plus, per query and hop, the k most attended slots of the one
+        memory and their probabilities: (u_out, top_slot int32 [B][H][k], top_p float32 [B][H][k]), larger probability first,
+        equal probabilities: lower slot first; entries past n_slots are slot -1 (0xFFFFFFFF), p 0."""
+        B = u0.shape[0]
+        assert keys.shape in ((self.H, n_slots, self.Dp), (1, n_slots, self.Dp)) and vals.shape == keys.shape
+        assert keys.is_contiguous() and vals.is_contiguous()
+        u_out = torch.empty_like(u0)
+        top_slot, top_p = _top_out(self.dev, B, self.H, k)
+        hop_stride = n_slots * self.Dp if keys.shape[0] == self.H else 0          # one plane for several hops: tied
+        abi.check(abi.lib.qmann_hops_shared_top_float_i8(C.byref(self.net), _ptr(keys), _ptr(vals), hop_stride, n_slots, _ptr(u0),
+                                                         _ptr(u_out), k, _ptr(top_slot), _ptr(top_p), B, self._s()),
+                  "qmann_hops_shared_top_float_i8")
+        return u_out, top_slot, top_p
+
     def hops_shared(self, keys, vals, n_slots, u0, taps=False, u_out=None):
         """qmann_hops_shared_i8: ONE memory for every query.  keys/vals int8 [H][n_slots][Dp], or [1][n_slots][Dp] for tied
         hops (hop stride 0); u0 [B][D] float.  taps: score_codes / scores / probs [H][B][n_slots], o / u [B][H][D]."""
@@ -686,6 +716,19 @@ class HostModel:
                   "qmann_model_forward_words_top")
         return pred, cost, match, top_slot, top_p
 
+    def forward_words_top_float(self, story_words, question_words, row_off, max_slots, k, answer=None):
+        """qmann_model_forward_words_top_float: forward_words_top for a float-attention model -- rows as QNet.hops_top_float
+        gives them"""
+        B = question_words.shape[0]
+        pred, cost, match = self._out(B, answer)
+        top_slot, top_p = _top_out(self.dev, B, self.cfg["n_hop"], k)
+        abi.check(abi.lib.qmann_model_forward_words_top_float(self.h, _ptr(story_words), story_words.shape[0], story_words.shape[1],
+                                                              _ptr(question_words), question_words.shape[1], _ptr(row_off),
+                                                              max_slots, B, _ptr(answer), _ptr(pred), _ptr(cost), _ptr(match),
+                                                              k, _ptr(top_slot), _ptr(top_p), self._s()),
+                  "qmann_model_forward_words_top_float")
+        return pred, cost, match, top_slot, top_p
+
     def forward_shared_words(self, story_words, question_words, answer=None):
         """qmann_model_forward_shared_words: one story [n_rows][W], every question of question_words [B][Wq] attends to it"""
         B = question_words.shape[0]
@@ -749,6 +792,18 @@ class HostModel:
         abi.check(abi.lib.qmann_model_ask_words_top_packed(self.h, _ptr(question_words), question_words.shape[1], B, _ptr(answer),
                                                            _ptr(pred), _ptr(cost), _ptr(match), k, _ptr(top_slot), _ptr(top_p),
                                                            self._s()), "qmann_model_ask_words_top_packed")
+        return pred, cost, match, top_slot, top_p
+
+    def ask_words_top_float(self, question_words, k, answer=None):
+        """qmann_model_ask_words_top_float: ask_words_top for a float-attention model with float asks enabled -- (pred, cost,
+        match, top_slot int32 [B][H][k], top_p float32 [B][H][k]), rows of the memorised story as QNet.hops_shared_top_float
+        gives them"""
+        B = question_words.shape[0]
+        pred, cost, match = self._out(B, answer)
+        top_slot, top_p = _top_out(self.dev, B, self.cfg["n_hop"], k)
+        abi.check(abi.lib.qmann_model_ask_words_top_float(self.h, _ptr(question_words), question_words.shape[1], B, _ptr(answer),
+                                                          _ptr(pred), _ptr(cost), _ptr(match), k, _ptr(top_slot), _ptr(top_p),
+                                                          self._s()), "qmann_model_ask_words_top_float")
         return pred, cost, match, top_slot, top_p
 
     def forward_bow(self, story, question, row_off, max_slots, answer=None):
