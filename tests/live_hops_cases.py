@@ -188,12 +188,15 @@ def _att_input(cfg, u, h):
     return np.maximum(u, 0).astype(np.float32) if cfg.get("en_non_lin") and h > 0 else u
 
 
-def _hot_key_fixed(oracle, cfg, h, u_att, amp, delta):
+def _hot_key_fixed(oracle, cfg, h, u_att, amp, delta, cols=None):
     """delta = 0: sign(u_h) . amp in every column where u_h is not zero, a score that saturates at the top code.  delta > 0:
-    columns are added, strong ones first and then single codes, as long as the oracle's score stays at or under top - delta"""
+    columns are added, strong ones first and then single codes, as long as the oracle's score stays at or under top - delta.
+    cols: the columns the key may use (default: all)"""
     (ia, fa), fb = cfg["fmt_att"][h], cfg["fmt_bin"]
     top = ((1 << (ia + fa)) - 1) / float(1 << fa)
     sgn = np.sign(u_att).astype(np.int64)
+    if cols is not None:
+        sgn = sgn * np.isin(np.arange(len(sgn)), cols)
     if delta <= 0:
         return sgn * amp
     score = lambda k: float(oracle.dot_mat_vec_fwd((k / float(1 << fa)).astype(np.float32)[None], u_att, False, True, (ia, fa), fb)[0])
@@ -214,6 +217,49 @@ def _hot_key_ham(cfg, h, u_att, delta):
     turn = np.nonzero(key)[0][:int(round(delta * (4 if cfg["attention_mode"] == 3 else 1)))]
     key[turn] = -key[turn]
     return key
+
+
+def cold_memory(rng, P, R, D, mode, fmt_att, fmt, sigma_cold, density, sigma_v):
+    """P planes of R cold rows (plane p on the grids fmt_att[p] / fmt[p]): sparse keys near zero (Hamming modes: dense random
+    codes) and dense random values -> keys, vals int8 codes [P][R][Dp]"""
+    Dp = pad_dim(D)
+    keys = np.zeros((P, R, Dp), np.int8); vals = np.zeros((P, R, Dp), np.int8)
+    for h in range(P):
+        mk, mv = (1 << sum(fmt_att[h])) - 1, (1 << sum(fmt[h])) - 1
+        if mode == 2:
+            k = np.rint(rng.normal(0, sigma_cold, (R, D))) * (rng.random((R, D)) < density * min(1.0, 60.0 / D))
+        else:
+            k = np.rint(rng.normal(0, 40, (R, D)))
+        keys[h, :, :D] = np.clip(k, -min(mk, 127), min(mk, 127))
+        vals[h, :, :D] = np.clip(np.rint(rng.normal(0, sigma_v, (R, D))), -min(mv, 127), min(mv, 127))
+    return keys, vals
+
+
+def linear_maps(rng, H, D, fmt_w, lin_density):
+    """a signed permutation at 1.0 (or the format's top code), so that every hop's state reaches the output, plus sparse single
+    codes -> w_h, float32 [D][D] per hop.  (A dense Gaussian map saturates the later hops' states.)"""
+    lin = []
+    for h in range(H):
+        one = min(1 << fmt_w[h][1], (1 << sum(fmt_w[h])) - 1)
+        m = np.sign(rng.normal(0, 1, (D, D))) * (rng.random((D, D)) < lin_density / np.sqrt(D))
+        m[np.arange(D), rng.permutation(D)] = one * np.where(rng.random(D) < 0.5, -1, 1)
+        lin.append(m)
+    return [(lin[h] / float(1 << fmt_w[h][1])).astype(np.float32) for h in range(H)]
+
+
+def first_states(rng, B, D, fmt_w0, sigma_u):
+    """u0 float32 [B][D] on hop 0's weight grid, no column zero"""
+    m0 = min((1 << sum(fmt_w0)) - 1, 127)
+    u0c = np.clip(np.rint(rng.normal(0, sigma_u, (B, D))), -m0, m0)
+    u0c[u0c == 0] = 1
+    return (u0c / float(1 << fmt_w0[1])).astype(np.float32)
+
+
+def loud_values(v, v_min, mv):
+    """a hot row's value codes: none below v_min in magnitude, so that the row's term shows in every column"""
+    v = v.astype(np.int64)
+    v = np.where(np.abs(v) < v_min, np.where(v < 0, -v_min, v_min), v)
+    return np.clip(v, -mv, mv)
 
 
 NUDGES = (None, 3.0, 2.75, 3.25, 2.5, 3.5, 2.25, 2.0, 3.75, 1.75, 4.0, 1.5)
@@ -237,29 +283,11 @@ def plant(oracle, name, family, S_in, D=60, H=3, mode=2, fmt=Q52, fmt_att=None, 
     row_off = np.concatenate([[0], np.cumsum(S_in)]).astype(np.int64)
     R = max(int(row_off[-1]), 1)
     ms = int(max_slots if max_slots is not None else max(S_in))
-    keys = np.zeros((H, R, Dp), np.int8); vals = np.zeros((H, R, Dp), np.int8)
-    for h in range(H):
-        mk, mv = (1 << sum(fmt_att[h])) - 1, (1 << sum(fmt[h])) - 1
-        if mode == 2:
-            k = np.rint(rng.normal(0, sigma_cold, (R, D))) * (rng.random((R, D)) < density * min(1.0, 60.0 / D))
-        else:
-            k = np.rint(rng.normal(0, 40, (R, D)))
-        keys[h, :, :D] = np.clip(k, -min(mk, 127), min(mk, 127))
-        vals[h, :, :D] = np.clip(np.rint(rng.normal(0, sigma_v, (R, D))), -min(mv, 127), min(mv, 127))
+    keys, vals = cold_memory(rng, len(fmt), R, D, mode, fmt_att, fmt, sigma_cold, density, sigma_v)
     wts = dict(w_ans=np.zeros((4, D), np.float32))
     if cfg["en_lin_map"]:
-        # a signed permutation at 1.0 (or the format's top code), so that every hop's state reaches the output, plus sparse single codes
-        lin = []
-        for h in range(H):
-            one = min(1 << fmt_w[h][1], (1 << sum(fmt_w[h])) - 1)
-            m = np.sign(rng.normal(0, 1, (D, D))) * (rng.random((D, D)) < lin_density / np.sqrt(D))
-            m[np.arange(D), rng.permutation(D)] = one * np.where(rng.random(D) < 0.5, -1, 1)
-            lin.append(m)
-        wts["w_h"] = [(lin[h] / float(1 << fmt_w[h][1])).astype(np.float32) for h in range(H)]
-    m0 = min((1 << sum(fmt_w[0])) - 1, 127)
-    u0c = np.clip(np.rint(rng.normal(0, sigma_u, (B, D))), -m0, m0)
-    u0c[u0c == 0] = 1
-    u0 = (u0c / float(1 << fmt_w[0][1])).astype(np.float32)
+        wts["w_h"] = linear_maps(rng, H, D, fmt_w, lin_density)
+    u0 = first_states(rng, B, D, fmt_w[0], sigma_u)
     case = Case(name, family, cfg, wts, keys, vals, row_off, u0, ms, dict(env or {}), packed, min_live, tuple(positions),
                 taps_too=taps_too)
     model = _model(oracle, cfg, wts, H)
@@ -288,9 +316,7 @@ def plant(oracle, name, family, S_in, D=60, H=3, mode=2, fmt=Q52, fmt_att=None, 
             spare = [r for r in spread if r not in rows][0] if S > len(rows) else None
             for r, dl in zip(rows, dls):
                 keys[h, r0 + r, :D] = hot_key(dl)
-                v = vals[h, r0 + r, :D].astype(np.int64)
-                v = np.where(np.abs(v) < v_min, np.where(v < 0, -v_min, v_min), v)
-                vals[h, r0 + r, :D] = np.clip(v, -mv, mv)
+                vals[h, r0 + r, :D] = loud_values(vals[h, r0 + r, :D], v_min, mv)
             if behind_cut and s_in > ms:                  # the row behind the cut: every column at full strength, a loud value row
                 keys[h, r0 + ms, :D] = np.sign(u_att) * full if mode == 2 else _hot_key_ham(cfg, h, u_att, 0)
                 vals[h, r0 + ms, :D] = np.where(np.arange(D) % 2 == 0, mv, -mv)
@@ -511,12 +537,18 @@ def simulate(oracle, case, taps=ALL_TAPS, fault=None):
       "drop_row"      leaves one live row's term out of o (the oracle with that value row zeroed);
       "swap_weights"  gives two live rows each other's weight (the oracle with their value rows swapped);
       "hop0_plane"    reads hop 1's values from hop 0's plane;
-      "behind_cut"    scores and reads one row more than max_slots allows."""
+      "behind_cut"    scores and reads one row more than max_slots allows;
+      a callable      reads other value planes (shared_live_cases.py has its faults in this form)."""
     ref = list(reference(oracle, case))
     if fault:
-        q, h = fault_applies(case, ref, fault)
+        if callable(fault):                               # (case, ref) -> (query, the value planes that query reads instead)
+            q, vals = fault(case, ref)
+            h = 0
+        else:
+            q, h = fault_applies(case, ref, fault)
+            vals = case.vals.copy()
         r0, S, _ = case.slots(q)
-        vals, n = case.vals.copy(), S
+        n = S
         wc = weight_codes(ref[q]["probs"][h], case.cfg["fmt"][h][1])
         lv = np.nonzero(wc)[0]
         if fault == "drop_row":
