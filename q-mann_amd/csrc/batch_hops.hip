@@ -37,6 +37,7 @@
 //      a unit's rows add the rows' terms to the workgroup's sum, THEN the wavefront looks at that sum (its own unit included),
 //      and only then asks for another unit.
 #include "hops_mid.h"
+#include "hops_float_common.h"      // (float_story_lds_bytes: the float launcher's refusal, said here for the top call)
 #include "hops_host.h"
 
 namespace {
@@ -353,7 +354,7 @@ int qm_hops_i8(const qmann_net *net, const int8_t *keys, const int8_t *vals, siz
     if (const int rc = fill_hop_args(a, net, keys, vals, hop_stride, hop_stride, row_off, u0, u_out, taps, hints.plane_rows)) return rc;
     a.max_slots = max_slots;
     const size_t lds = qmann_hops_lds_bytes(max_slots);
-    if (lds > 160 * 1024 - 1024) return QMANN_ERANGE;   // a little static LDS is used besides
+    if (lds > kHopLdsLimit) return QMANN_ERANGE;
     if (n_query == 0) return QMANN_OK;
     if (qm_too_many_queries(n_query)) return QMANN_ERANGE;
 
@@ -361,7 +362,7 @@ int qm_hops_i8(const qmann_net *net, const int8_t *keys, const int8_t *vals, siz
         if (hints.top_float) return qmann_hops_top_float_impl(a, net->dim_emb_pad, max_slots, hints.top_k, hints.top_slot, hints.top_p, n_query, stream);
         // (attended slots through qmann_hops_top_i8: float attention is not served -- behind the one refusal the float launcher
         // has of its own; qmann_hops_top_float_i8 is the call that serves it)
-        if (hints.top_on) return (size_t)kOffScores + (((size_t)max_slots * 4 + 15) & ~(size_t)15) > 160 * 1024 - 1024 ? QMANN_ERANGE : QMANN_EUNSUPPORTED;
+        if (hints.top_on) return float_story_lds_bytes(max_slots) > kHopLdsLimit ? QMANN_ERANGE : QMANN_EUNSUPPORTED;
         return qmann_hops_float_impl(a, net->dim_emb_pad, max_slots, n_query, stream);
     }
     if (hints.top_float) return QMANN_EUNSUPPORTED;       // (qmann_hops_top_float_i8: float attention only)

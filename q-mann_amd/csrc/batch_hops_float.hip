@@ -10,7 +10,7 @@
 // v_perm + v_bfi) and is bit-identical to the reference's float sum in any order.  The read-out
 // o[c] = sum_r p[r] . C[r][c] is a genuine float sum over ALL slots (p is not quantised), so this
 // mode streams the value plane as well; its result carries the float-order tolerance (1e-5).
-#include "hops_common.h"
+#include "hops_float_common.h"      // (float_story_lds_bytes; this kernel keeps its own text of the stages)
 
 namespace {
 
@@ -213,8 +213,8 @@ extern "C" int qmann_hops_float_impl(const HopArgs &a, uint32_t Dp, uint32_t max
 {
     QmBatched qm_scope;
     static_assert(kOffHist + 1024 + kWaves * 256 * 4 <= kOffU, "partial sums must fit the histogram + p-table area");
-    const size_t lds = (size_t)kOffScores + (((size_t)max_slots * 4 + 15) & ~(size_t)15);
-    if (lds > 160 * 1024 - 1024) return QMANN_ERANGE;
+    const size_t lds = float_story_lds_bytes(max_slots);
+    if (lds > kHopLdsLimit) return QMANN_ERANGE;
     hipStream_t st = (hipStream_t)stream;
     qm_dispatch<4, 8, 16>(Dp / 16, [&](auto lpr) { qm_launch(k_hops_float<decltype(lpr)::value>, n_query, kBlock, lds, st, a); });
     QM_LAUNCH_CHECK();

@@ -292,7 +292,7 @@ int ham_prepare(HopArgs &a, size_t &lds, const qmann_net *net, const void *keys,
     a.max_slots = max_slots;
     const bool v0 = net->attention_mode == QMANN_ATT_HAMMING_V0;       // (the only mode with a table of bins)
     lds = ham_lds_bytes(max_slots, v0 ? net->num_bit * net->dim_emb + 1u : 0u);
-    if (lds > 160 * 1024 - 1024) return QMANN_ERANGE;
+    if (lds > kHopLdsLimit) return QMANN_ERANGE;
     if (late_rc) return late_rc;
     if (n_query == 0) return QMANN_OK;
     if (qm_too_many_queries(n_query)) return QMANN_ERANGE;

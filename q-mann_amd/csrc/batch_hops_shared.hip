@@ -18,7 +18,7 @@
 
 namespace {
 
-// (kSharedLdsLimit, QueryLds and scan_rows_shared: hops_shared.h, shared with batch_hops_shared_split.hip)
+// (QueryLds and scan_rows_shared: hops_shared.h, shared with batch_hops_shared_split.hip; the call prelude: hops_host.h)
 // per_q: bytes of LDS per query (qmann_hops_lds_bytes(n_slots)); a.max_slots = n_slots >= 1
 // TOP (qmann_hops_shared_top_i8): behind every query's hop its k most attended slots go to tp.slot / tp.p (hops_attended.h).
 // The TOP builds are instantiations of their own: the others take an EMPTY last argument and keep their device code.
@@ -109,7 +109,7 @@ k_hops_shared(const HopArgs a, const uint32_t n_query, const uint32_t per_q, con
 uint32_t choose_qt(uint32_t n_slots, uint32_t n_query)
 {
     uint32_t fit = 8;
-    while (fit > 1 && qmann_hops_shared_lds_bytes(n_slots, fit) > kSharedLdsLimit) fit >>= 1;
+    while (fit > 1 && qmann_hops_shared_lds_bytes(n_slots, fit) > kHopLdsLimit) fit >>= 1;
     const uint32_t forced = qm_tuning().shared_qt;
     if (forced) return forced < fit ? forced : fit;
     const uint32_t want = n_slots >= 4096u ? 4u : 2u;
@@ -129,7 +129,7 @@ size_t qmann_hops_shared_lds_bytes(uint32_t n_slots, uint32_t queries_per_group)
 
 uint32_t qmann_hops_shared_tile(uint32_t n_slots, uint32_t n_query)
 {
-    if (n_slots == 0 || n_query == 0 || qmann_hops_shared_lds_bytes(n_slots, 1) > kSharedLdsLimit) return 0;
+    if (n_slots == 0 || n_query == 0 || qmann_hops_shared_lds_bytes(n_slots, 1) > kHopLdsLimit) return 0;
     return choose_qt(n_slots, n_query);
 }
 
@@ -139,17 +139,13 @@ static int hops_shared_impl(const qmann_net *net, const int8_t *keys, const int8
                             const AttTop<true> *tp)
 {
     QmBatched qm_scope;
-    static const uint32_t no_row_off = 0;                     // this call has no row_off: the shared checks want a non-null one
-    if (const int rc = check_hop_call(net, keys, vals, &no_row_off, u0, u_out)) return rc;
+    // (the steps of hops_host.h's shared-plane prelude, this family's own refusals between them)
+    if (const int rc = shared_open(net, keys, vals, u0, u_out)) return rc;
     if (net->attention_mode != QMANN_ATT_FIXED) return QMANN_EUNSUPPORTED;
     HopArgs a;
-    if (const int rc = fill_hop_args(a, net, keys, vals, hop_stride, hop_stride, &no_row_off, u0, u_out, taps)) return rc;
-    if (n_slots == 0) return QMANN_EINVAL;
-    a.row_off = nullptr;
-    a.max_slots = a.rows_total = n_slots;
-    if (qmann_hops_shared_lds_bytes(n_slots, 1) > kSharedLdsLimit) return QMANN_ERANGE;
-    if (n_query == 0) return QMANN_OK;
-    if (qm_too_many_queries(n_query)) return QMANN_ERANGE;
+    if (const int rc = shared_fill(a, net, keys, vals, hop_stride, hop_stride, n_slots, u0, u_out, taps)) return rc;
+    if (qmann_hops_shared_lds_bytes(n_slots, 1) > kHopLdsLimit) return QMANN_ERANGE;
+    if (int rc; shared_no_queries(n_query, rc)) return rc;
     if (tp && !att_top_args_ok(tp->k, tp->slot, tp->p)) return QMANN_EINVAL;     // behind every refusal of the base call
 
     const bool w7 = !qm_tuning().no_w7 && all_w7(a, kW7Att);

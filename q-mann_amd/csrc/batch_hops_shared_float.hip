@@ -22,8 +22,6 @@
 
 namespace {
 
-constexpr size_t kSharedFloatLdsLimit = 160 * 1024 - 1024;     // as qmann_hops_i8: a little static LDS is used besides
-
 // per_q: bytes of LDS per query (qmann_hops_shared_float_lds_bytes(n_slots, 1)); a.max_slots = n_slots >= 1
 template <int LPR, int QT>
 __global__ void __launch_bounds__(kBlock)
@@ -200,7 +198,7 @@ uint32_t choose_float_qt(uint32_t n_slots, uint32_t n_query)
 {
     (void)n_query;
     uint32_t fit = 8;
-    while (fit > 1 && qmann_hops_shared_float_lds_bytes(n_slots, fit) > kSharedFloatLdsLimit) fit >>= 1;
+    while (fit > 1 && qmann_hops_shared_float_lds_bytes(n_slots, fit) > kHopLdsLimit) fit >>= 1;
     const uint32_t forced = qm_tuning().shared_qt;
     if (forced) return forced < fit ? forced : fit;
     return 1;
@@ -217,7 +215,7 @@ size_t qmann_hops_shared_float_lds_bytes(uint32_t n_slots, uint32_t queries_per_
 
 uint32_t qmann_hops_shared_float_tile(uint32_t n_slots, uint32_t n_query)
 {
-    if (n_slots == 0 || n_query == 0 || qmann_hops_shared_float_lds_bytes(n_slots, 1) > kSharedFloatLdsLimit) return 0;
+    if (n_slots == 0 || n_query == 0 || qmann_hops_shared_float_lds_bytes(n_slots, 1) > kHopLdsLimit) return 0;
     return choose_float_qt(n_slots, n_query);
 }
 
@@ -226,17 +224,13 @@ int qmann_hops_shared_float_i8(const qmann_net *net, const int8_t *keys, const i
 {
     QmBatched qm_scope;
     static_assert(kOffScores % 16 == 0, "a query's slice starts 16-byte aligned");
-    static const uint32_t no_row_off = 0;                     // this call has no row_off: the shared checks want a non-null one
-    if (const int rc = check_hop_call(net, keys, vals, &no_row_off, u0, u_out)) return rc;
+    // (the steps of hops_host.h's shared-plane prelude; the float calls' mode is refused BEHIND the formats, inside the fill)
+    if (const int rc = shared_open(net, keys, vals, u0, u_out)) return rc;
     HopArgs a;
-    if (const int rc = fill_hop_args(a, net, keys, vals, hop_stride, hop_stride, &no_row_off, u0, u_out, taps)) return rc;
-    if (net->attention_mode != QMANN_ATT_FLOAT) return QMANN_EUNSUPPORTED;
-    if (n_slots == 0) return QMANN_EINVAL;
-    a.row_off = nullptr;
-    a.max_slots = a.rows_total = n_slots;
-    if (qmann_hops_shared_float_lds_bytes(n_slots, 1) > kSharedFloatLdsLimit) return QMANN_ERANGE;
-    if (n_query == 0) return QMANN_OK;
-    if (qm_too_many_queries(n_query)) return QMANN_ERANGE;
+    if (const int rc = shared_fill(a, net, keys, vals, hop_stride, hop_stride, n_slots, u0, u_out, taps, nullptr,
+                                   net->attention_mode == QMANN_ATT_FLOAT)) return rc;
+    if (qmann_hops_shared_float_lds_bytes(n_slots, 1) > kHopLdsLimit) return QMANN_ERANGE;
+    if (int rc; shared_no_queries(n_query, rc)) return rc;
 
     const uint32_t qt = choose_float_qt(n_slots, n_query), per_q = (uint32_t)qmann_hops_shared_float_lds_bytes(n_slots, 1);
     qm_dispatch<4, 8, 16>(net->dim_emb_pad / 16, [&](auto lpr) {

@@ -20,9 +20,8 @@
 
 namespace {
 
-constexpr size_t kSharedLdsLimit = 160 * 1024 - 1024;          // as qmann_hops_packed: a little static LDS is used besides
-
-// (HamQueryLds, PlaneQuery and scan_planes_shared: hops_shared_ham.h, shared with batch_hops_shared_split_ham.hip)
+// (HamQueryLds, PlaneQuery and scan_planes_shared: hops_shared_ham.h, shared with batch_hops_shared_split_ham.hip; the call
+// prelude: hops_host.h)
 
 // LPRK: lanes per key row (16 LPRK bytes); DP: padded embedding width; MODE: kModeV0 / kModeV1; NB: planes; QT: queries per
 // workgroup.  per_q: bytes of LDS per query (ham_lds_bytes); a.max_slots = n_slots >= 1
@@ -126,7 +125,7 @@ k_hops_shared_ham(const HopArgs a, const uint32_t n_query, const uint32_t per_q,
 uint32_t choose_qt_ham(size_t per_q, uint32_t n_query)
 {
     uint32_t fit = 8;
-    while (fit > 1 && fit * per_q > kSharedLdsLimit) fit >>= 1;
+    while (fit > 1 && fit * per_q > kHopLdsLimit) fit >>= 1;
     const uint32_t forced = qm_tuning().shared_qt;
     if (forced) return forced < fit ? forced : fit;
     uint32_t qt = fit < 4u ? fit : 4u;
@@ -148,7 +147,7 @@ uint32_t qmann_hops_shared_packed_tile(const qmann_net *net, uint32_t n_slots, u
 {
     if (!net || !packed_form_ok(net) || n_slots == 0 || n_query == 0) return 0;
     const size_t per_q = ham_lds_bytes(n_slots, v0_bins_of(net));
-    if (per_q > kSharedLdsLimit) return 0;
+    if (per_q > kHopLdsLimit) return 0;
     return choose_qt_ham(per_q, n_query);
 }
 
@@ -158,22 +157,18 @@ static int hops_shared_packed_impl(const qmann_net *net, const uint64_t *key_pla
                                    uint32_t n_query, void *stream, const HamTop<true> *tp)
 {
     QmBatched qm_scope;
-    static const uint32_t no_row_off = 0;                     // this call has no row_off: the shared checks want a non-null one
-    if (const int rc = check_hop_call(net, key_planes, vals, &no_row_off, u0, u_out)) return rc;
+    // (the steps of hops_host.h's shared-plane prelude, this family's own refusals between them)
+    if (const int rc = shared_open(net, key_planes, vals, u0, u_out)) return rc;
     if (!packed_form_ok(net)) return QMANN_EUNSUPPORTED;
     const uint32_t nb = net->num_bit, Dp = net->dim_emb_pad;
     if (key_hop_stride != val_hop_stride / Dp * (Dp / 64) * nb * 8) return QMANN_EINVAL;
     if ((uintptr_t)key_planes & 15u) return QMANN_EINVAL;     // 16-byte loads
     HopArgs a;
-    if (const int rc = fill_hop_args(a, net, key_planes, vals, key_hop_stride, val_hop_stride, &no_row_off, u0, u_out, taps, 0, check_ham_hop)) return rc;
-    if (n_slots == 0) return QMANN_EINVAL;
-    a.row_off = nullptr;
-    a.max_slots = a.rows_total = n_slots;
+    if (const int rc = shared_fill(a, net, key_planes, vals, key_hop_stride, val_hop_stride, n_slots, u0, u_out, taps, check_ham_hop)) return rc;
     const size_t per_q = ham_lds_bytes(n_slots, v0_bins_of(net));
-    if (per_q > kSharedLdsLimit) return QMANN_ERANGE;
+    if (per_q > kHopLdsLimit) return QMANN_ERANGE;
     if (Dp / 64 * nb * 8 < 16) return QMANN_EUNSUPPORTED;     // Dp = 64 with a single plane: a key row is half a 16-byte load
-    if (n_query == 0) return QMANN_OK;
-    if (qm_too_many_queries(n_query)) return QMANN_ERANGE;
+    if (int rc; shared_no_queries(n_query, rc)) return rc;
     if (tp && !ham_top_args_ok(tp->k, tp->slot, tp->p)) return QMANN_EINVAL;     // behind every refusal of the base call
 
     const bool v1 = net->attention_mode == QMANN_ATT_HAMMING_V1;

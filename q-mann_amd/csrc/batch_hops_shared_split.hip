@@ -220,17 +220,14 @@ static int hops_shared_split_impl(const qmann_net *net, const int8_t *keys, cons
                                   void *ws, size_t ws_bytes, void *stream, const AttTop<true> *tp)
 {
     QmBatched qm_scope;
-    static const uint32_t no_row_off = 0;                     // this call has no row_off: the shared checks want a non-null one
-    if (const int rc = check_hop_call(net, keys, vals, &no_row_off, u0, u_out)) return rc;
+    // (the steps of hops_host.h's shared-plane prelude, this family's own refusals between them; no LDS refusal: the slots are cut)
+    if (const int rc = shared_open(net, keys, vals, u0, u_out)) return rc;
     if (net->attention_mode != QMANN_ATT_FIXED) return QMANN_EUNSUPPORTED;
     HopArgs a;
-    if (const int rc = fill_hop_args(a, net, keys, vals, hop_stride, hop_stride, &no_row_off, u0, u_out, taps)) return rc;
-    if (n_slots == 0 || !ws || ((uintptr_t)ws & 15u)) return QMANN_EINVAL;
+    if (const int rc = shared_fill(a, net, keys, vals, hop_stride, hop_stride, n_slots, u0, u_out, taps)) return rc;
+    if (!ws || ((uintptr_t)ws & 15u)) return QMANN_EINVAL;
     if (n_slots > kSplitMaxSlots) return QMANN_ERANGE;
-    a.row_off = nullptr;
-    a.max_slots = a.rows_total = n_slots;
-    if (n_query == 0) return QMANN_OK;
-    if (qm_too_many_queries(n_query)) return QMANN_ERANGE;
+    if (int rc; shared_no_queries(n_query, rc)) return rc;
     if (ws_bytes < qmann_hops_shared_split_ws_bytes(net, n_slots, n_query)) return QMANN_EINVAL;
     if (tp && !att_top_args_ok(tp->k, tp->slot, tp->p)) return QMANN_EINVAL;     // behind every refusal of the base call
 

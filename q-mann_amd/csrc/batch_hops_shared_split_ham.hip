@@ -277,22 +277,18 @@ static int hops_shared_split_packed_impl(const qmann_net *net, const uint64_t *k
                                          void *stream, const HamTop<true> *tp)
 {
     QmBatched qm_scope;
-    static const uint32_t no_row_off = 0;                     // this call has no row_off: the shared checks want a non-null one
-    if (const int rc = check_hop_call(net, key_planes, vals, &no_row_off, u0, u_out)) return rc;
+    // (the steps of hops_host.h's shared-plane prelude, this family's own refusals between them; no LDS refusal: the slots are cut)
+    if (const int rc = shared_open(net, key_planes, vals, u0, u_out)) return rc;
     if (!packed_form_ok(net)) return QMANN_EUNSUPPORTED;
     const uint32_t nb = net->num_bit, Dp = net->dim_emb_pad;
     if (key_hop_stride != val_hop_stride / Dp * (Dp / 64) * nb * 8) return QMANN_EINVAL;
     if ((uintptr_t)key_planes & 15u) return QMANN_EINVAL;     // 16-byte loads
     HopArgs a;
-    if (const int rc = fill_hop_args(a, net, key_planes, vals, key_hop_stride, val_hop_stride, &no_row_off, u0, u_out, taps, 0, check_ham_hop)) return rc;
-    if (n_slots == 0) return QMANN_EINVAL;
+    if (const int rc = shared_fill(a, net, key_planes, vals, key_hop_stride, val_hop_stride, n_slots, u0, u_out, taps, check_ham_hop)) return rc;
     if (Dp / 64 * nb * 8 < 16) return QMANN_EUNSUPPORTED;     // Dp = 64 with a single plane: a key row is half a 16-byte load
     if (!ws || ((uintptr_t)ws & 15u)) return QMANN_EINVAL;
     if (n_slots > kSplitMaxSlots) return QMANN_ERANGE;
-    a.row_off = nullptr;
-    a.max_slots = a.rows_total = n_slots;
-    if (n_query == 0) return QMANN_OK;
-    if (qm_too_many_queries(n_query)) return QMANN_ERANGE;
+    if (int rc; shared_no_queries(n_query, rc)) return rc;
     if (ws_bytes < (size_t)n_query * split_bytes_per_query(net, n_slots)) return QMANN_EINVAL;
     if (tp && !ham_top_args_ok(tp->k, tp->slot, tp->p)) return QMANN_EINVAL;     // behind every refusal of the base call
 

@@ -17,8 +17,6 @@
 
 namespace {
 
-constexpr size_t kTopFloatLdsLimit = 160 * 1024 - 1024;       // as the base calls: a little static LDS is used besides
-
 // STORY: QT = 1, per_q unused.  Shared: per_q = bytes of LDS per query, a.max_slots = n_slots >= 1, a.row_off unused
 template <int LPR, int QT, bool STORY>
 __global__ void __launch_bounds__(kBlock)
@@ -209,8 +207,8 @@ extern "C" int qmann_hops_top_float_impl(const HopArgs &a, uint32_t Dp, uint32_t
                                          uint32_t n_query, void *stream)
 {
     QmBatched qm_scope;
-    const size_t lds = (size_t)kOffScores + (((size_t)max_slots * 4 + 15) & ~(size_t)15);
-    if (lds > kTopFloatLdsLimit) return QMANN_ERANGE;                      // (the float launcher's own refusal)
+    const size_t lds = float_story_lds_bytes(max_slots);
+    if (lds > kHopLdsLimit) return QMANN_ERANGE;                      // (the float launcher's own refusal)
     if (!att_top_args_ok(k, top_slot, top_p)) return QMANN_EINVAL;         // behind every refusal of the base call
     const AttTop<true> tp{top_slot, top_p, k};
     qm_dispatch<4, 8, 16>(Dp / 16, [&](auto lpr) {
@@ -228,17 +226,12 @@ int qmann_hops_shared_top_float_i8(const qmann_net *net, const int8_t *keys, con
 {
     QmBatched qm_scope;
     // qmann_hops_shared_float_i8's refusals, in its order
-    static const uint32_t no_row_off = 0;                     // this call has no row_off: the shared checks want a non-null one
-    if (const int rc = check_hop_call(net, keys, vals, &no_row_off, u0, u_out)) return rc;
+    if (const int rc = shared_open(net, keys, vals, u0, u_out)) return rc;
     HopArgs a;
-    if (const int rc = fill_hop_args(a, net, keys, vals, hop_stride, hop_stride, &no_row_off, u0, u_out, nullptr)) return rc;
-    if (net->attention_mode != QMANN_ATT_FLOAT) return QMANN_EUNSUPPORTED;
-    if (n_slots == 0) return QMANN_EINVAL;
-    a.row_off = nullptr;
-    a.max_slots = a.rows_total = n_slots;
-    if (qmann_hops_shared_float_lds_bytes(n_slots, 1) > kTopFloatLdsLimit) return QMANN_ERANGE;
-    if (n_query == 0) return QMANN_OK;
-    if (qm_too_many_queries(n_query)) return QMANN_ERANGE;
+    if (const int rc = shared_fill(a, net, keys, vals, hop_stride, hop_stride, n_slots, u0, u_out, nullptr, nullptr,
+                                   net->attention_mode == QMANN_ATT_FLOAT)) return rc;
+    if (qmann_hops_shared_float_lds_bytes(n_slots, 1) > kHopLdsLimit) return QMANN_ERANGE;
+    if (int rc; shared_no_queries(n_query, rc)) return rc;
     if (!att_top_args_ok(k, top_slot, top_p)) return QMANN_EINVAL;         // behind every refusal of the base call
 
     const AttTop<true> tp{top_slot, top_p, k};

@@ -1,5 +1,6 @@
 // hops_float_common.h -- stages of float attention (ATTENTION_MODE 1) as functions, for the kernels that run them on a query's
-// slice of LDS (batch_hops_shared_float.hip).
+// slice of LDS (batch_hops_shared_float.hip, batch_hops_top_float.hip), and the LDS size of a per-story float launch
+// (batch_hops_float.hip and batch_hops_top_float.hip refuse by it).
 //
 // (COPIES of what k_hops_float carries inline, batch_hops_float.hip -- calling these from there changes that kernel's device
 // assembly (tools/device_asm_equal.sh), so it keeps its own text, as k_hops_fixed does beside hist_softmax_survivors; keep the
@@ -114,6 +115,9 @@ struct FloatQueryLds {
           kuq((int8_t *)(b + kOffHist)), red((double *)(b + kOffRed)), sc((int32_t *)(b + kOffScores)) {}
 };
 static_assert(kOffHist + 1024 + kWaves * 256 * 4 <= kOffU, "partial sums must fit the histogram + p-table area");
+
+// host side: the dynamic LDS of a per-story float launch -- the carve-up, then a score (later p) of four bytes per slot
+inline size_t float_story_lds_bytes(uint32_t max_slots) { return (size_t)kOffScores + (((size_t)max_slots * 4 + 15) & ~(size_t)15); }
 
 // hops_common.h::scan_rows<LPR, UN, false, kWaves> for a tile of QT queries on one plane: the same tiles, the same two in flight,
 // the same moved-back last tile.  retire(t, r, v): row r of query t has sum v; places t >= nq are computed and dropped.

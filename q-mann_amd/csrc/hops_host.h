@@ -1,5 +1,6 @@
-// hops_host.h -- the host side every hop entry point shares (batch_hops.hip, batch_hops_ham.hip): the checks of a hop call,
-// HopArgs from a qmann_net, and the choice of kernel for short memories.
+// hops_host.h -- the host side every hop entry point shares: the checks of a hop call and HopArgs from a qmann_net (all units),
+// the prelude of the shared-plane calls (batch_hops_shared*.hip, batch_hops_top_float.hip), and the choice of kernel for short
+// memories (batch_hops.hip, batch_hops_ham.hip).
 #pragma once
 #include "hops_lean.h"
 
@@ -69,6 +70,43 @@ inline int fill_hop_args(HopArgs &a, const qmann_net *net, const void *keys, con
     }
     a.rows_total = (uint32_t)(val_hop_stride ? val_hop_stride / net->dim_emb_pad : plane_rows);   // (tied hops: the caller's hint, or 0 = unknown)
     return QMANN_OK;
+}
+
+// ---- the shared-plane calls (one memory, every query reads it: n_slots in place of row_off and max_slots) ---------------------
+// The steps all eleven entry points take, in this order; a family's own refusals stay in its entry point, between them:
+//   shared_open        the pointers and sizes (check_hop_call)
+//                        [fixed-point: the attention mode; packed: packed_form_ok, key stride and alignment]
+//   shared_fill        fill_hop_args [float: the attention mode], then n_slots == 0, then HopArgs' row_off / max_slots / rows_total
+//                        [LDS size (not the split calls); packed: LPRK < 1; split: workspace pointer, kSplitMaxSlots]
+//   shared_no_queries  n_query == 0 is "OK, launch nothing"; too many queries
+//                        [split: workspace bytes; top: the top arguments, last]
+// The order is the order of the calls' return codes: tests/test_shared_call_refusals.py pins it.
+constexpr uint32_t no_row_off = 0;                             // these calls have no row_off: the shared checks want a non-null one
+
+inline int shared_open(const qmann_net *net, const void *keys, const int8_t *vals, const float *u0, const float *u_out)
+{
+    return check_hop_call(net, keys, vals, &no_row_off, u0, u_out);
+}
+
+// `mode_ok`: the float calls' attention-mode check, which they pass in because its refusal comes BEHIND the formats and ahead of
+// n_slots (the fixed-point and packed calls refuse their mode themselves, ahead of this step: both orders are documented)
+inline int shared_fill(HopArgs &a, const qmann_net *net, const void *keys, const int8_t *vals, size_t key_hop_stride, size_t val_hop_stride,
+                       uint32_t n_slots, const float *u0, float *u_out, const qmann_taps *taps,
+                       int (*family_check)(const qmann_net *, uint32_t) = nullptr, bool mode_ok = true)
+{
+    if (const int rc = fill_hop_args(a, net, keys, vals, key_hop_stride, val_hop_stride, &no_row_off, u0, u_out, taps, 0, family_check)) return rc;
+    if (!mode_ok) return QMANN_EUNSUPPORTED;
+    if (n_slots == 0) return QMANN_EINVAL;
+    a.row_off = nullptr;
+    a.max_slots = a.rows_total = n_slots;
+    return QMANN_OK;
+}
+
+// true: the call ends here with `rc`
+inline bool shared_no_queries(uint32_t n_query, int &rc)
+{
+    rc = n_query == 0 ? QMANN_OK : QMANN_ERANGE;
+    return n_query == 0 || qm_too_many_queries(n_query);
 }
 
 // May the fixed-point hop kernel end a key scan early (batch_hops.hip, step 1b and ScanStop)?  Only the e^x softmax without the

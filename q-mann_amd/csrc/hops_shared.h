@@ -1,12 +1,11 @@
 // hops_shared.h -- pieces of the shared-plane fixed-point hops (one memory, many queries) that more than one unit calls:
 // batch_hops_shared.hip (a workgroup walks the whole memory for its tile of queries) and batch_hops_shared_split.hip (the
-// memory cut into slices of slots, a workgroup per tile and slice).
+// memory cut into slices of slots, a workgroup per tile and slice).  Device pieces only: the calls' host side -- their prelude and
+// the LDS cap -- is hops_host.h's and rt.h's, shared with the float and packed units.
 #pragma once
 #include "hops_host.h"
 
 namespace {
-
-constexpr size_t kSharedLdsLimit = 160 * 1024 - 1024;          // as qmann_hops_i8: a little static LDS is used besides
 
 // one query's slice of the workgroup's LDS (hops_common.h's carve-up)
 struct QueryLds {

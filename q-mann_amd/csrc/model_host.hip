@@ -128,7 +128,6 @@ bool regrow(T **p, size_t n)
     return true;
 }
 
-constexpr size_t kAskLdsLimit = 160 * 1024 - 1024;        // what the shared-plane hop calls allow one query (their QMANN_ERANGE)
 // Asks of at most this many questions take the split call although the memory fits LDS.  NOT MEASURED (tools/shared_split_ab.py,
 // DESIGN.md section 5 "Measured, shared plane, split"): 0 = only memories that do not fit LDS take it.
 constexpr uint32_t kSplitAskMaxQueries = 0;
@@ -169,13 +168,17 @@ bool ask_splits(const qmann_model *m, uint32_t n_rows, uint32_t n_query)
     if (!m->split_bytes) return false;
     const size_t share = ask_split_share(m, n_rows);
     if (!share || share > m->split_bytes) return false;
-    return ask_lds_bytes(m, n_rows) > kAskLdsLimit || n_query <= (packed_mode(m->net) ? kSplitAskPackedMaxQueries : kSplitAskMaxQueries);
+    return ask_lds_bytes(m, n_rows) > kHopLdsLimit || n_query <= (packed_mode(m->net) ? kSplitAskPackedMaxQueries : kSplitAskMaxQueries);
 }
 
-// the body of the two enable calls: the workspace replaced by one of scratch_bytes (0: none), a memory that can no longer be
-// asked forgotten
-int set_split_workspace(qmann_model *m, size_t scratch_bytes, void *stream)
+// the two enable calls (they differ in `served`, the models each accepts -- never a float model: ask_words_impl relies on it):
+// the workspace replaced by one of scratch_bytes (0: none), a memory that can no longer be asked forgotten
+int enable_split_asks(qmann_model *m, bool (*served)(const qmann_model *), size_t scratch_bytes, void *stream)
 {
+    QmBatched qm_scope;
+    if (!m) return QMANN_EINVAL;
+    if (!served(m)) return QMANN_EUNSUPPORTED;
+    DeviceScope on(m->device);
     if (m->split_ws) {
         QM_HIP(hipStreamSynchronize((hipStream_t)stream));  // asks enqueued on it may still use the workspace that goes
         QM_HIP(hipFree(m->split_ws));
@@ -193,8 +196,8 @@ int set_split_workspace(qmann_model *m, size_t scratch_bytes, void *stream)
         }
     }
     // a memory only the split call can attend to, and no (or too small a) workspace for it: forgotten
-    if (m->mem_rows && ask_lds_bytes(m, m->mem_rows) > kAskLdsLimit && !ask_splits(m, m->mem_rows, 1)) m->mem_rows = 0;
-    return (scratch_bytes && !m->split_ws) ? QMANN_EHIP : QMANN_OK;
+    if (m->mem_rows && ask_lds_bytes(m, m->mem_rows) > kHopLdsLimit && !ask_splits(m, m->mem_rows, 1)) m->mem_rows = 0;
+    return (scratch_bytes && !m->split_ws) ? QMANN_EHIP : qm_scope.rc();
 }
 
 float *upload(const float *host, size_t n, hipStream_t st)
@@ -332,16 +335,37 @@ int ensure_float_matrices(qmann_model *m, void *stream)
     return QMANN_OK;
 }
 
-// hops + answer on the memories sitting in the workspace (hop planes rows_total . Dp apart; one shared plane when tied).
+// The end of every forward and ask, behind its hops: the float answer layer on m->u (`exact`: the serial-order kernels), then the
+// HIP failures the call's scope has seen, then last_n_query -- set only where all of it succeeded.
+int answer_and_finish(qmann_model *m, const QmBatched &scope, bool exact, uint32_t n_query, const uint32_t *answer, uint32_t *pred,
+                      float *cost, uint32_t *match, void *stream)
+{
+    int rc = (exact ? qmann_answer_f32_serial : qmann_answer_f32)(&m->net, m->w_ans, m->u, answer, pred, nullptr, cost, match, n_query, stream);
+    if (!rc) rc = scope.rc();
+    if (!rc) m->last_n_query = n_query;
+    return rc;
+}
+
+// the top fields of rt.h::QmHopHints for the forward_words_top calls (top_float: the float form), as the caller gave them
+QmHopHints top_hints(bool top_float, uint32_t k, uint32_t *top_slot, float *top_p)
+{
+    QmHopHints t;
+    t.top_on = true; t.top_float = top_float; t.top_k = k; t.top_slot = top_slot; t.top_p = top_p;
+    return t;
+}
+
+// hops + answer on the memories sitting in the workspace (hop planes rows_total . Dp apart; one shared plane when tied), and the
+// forward's last steps (answer_and_finish).
 // `split_ws`: the batch's index lists where with_side_branch below has made them, else null.
-// `top`: the attended slots of qmann_model_forward_words_top (rt.h::QmHopHints' top fields), or null.
-int hops_and_answer(qmann_model *m, uint32_t rows_total, const uint32_t *row_off, uint32_t max_slots, uint32_t n_query,
+// `top`: the attended slots of qmann_model_forward_words_top (top_hints), or null.
+int hops_and_answer(qmann_model *m, const QmBatched &scope, uint32_t rows_total, const uint32_t *row_off, uint32_t max_slots, uint32_t n_query,
                     const uint32_t *answer, uint32_t *pred, float *cost, uint32_t *match, void *stream, uint32_t *split_ws,
                     const QmHopHints *top = nullptr)
 {
     const size_t hop_stride = m->tied ? 0 : (size_t)rows_total * m->Dp;
-    QmHopHints hints{rows_total, split_ws};          // (a tied model passes hop_stride = 0: the hop kernels still learn the plane's size)
-    if (top) { hints.top_on = true; hints.top_float = top->top_float; hints.top_k = top->top_k; hints.top_slot = top->top_slot; hints.top_p = top->top_p; }
+    QmHopHints hints = top ? *top : QmHopHints{};
+    hints.plane_rows = rows_total;                   // (a tied model passes hop_stride = 0: the hop kernels still learn the plane's size)
+    hints.split_ws = split_ws;
     int rc;
     if (use_planes(m, max_slots)) {
         const size_t key_hop_stride = m->tied ? 0 : (size_t)rows_total * (m->Dp / 64) * m->net.num_bit * 8;
@@ -353,7 +377,7 @@ int hops_and_answer(qmann_model *m, uint32_t rows_total, const uint32_t *row_off
         rc = qm_hops_i8(&m->net, m->keys, m->vals, hop_stride, row_off, max_slots, m->u0, m->u, nullptr, n_query, stream, hints);
     }
     if (rc) return rc;
-    return (m->answer_exact ? qmann_answer_f32_serial : qmann_answer_f32)(&m->net, m->w_ans, m->u, answer, pred, nullptr, cost, match, n_query, stream);
+    return answer_and_finish(m, scope, m->answer_exact, n_query, answer, pred, cost, match, stream);
 }
 
 // The embedding step of a forward: `story(stream)` on the caller's stream and -- for large batches -- `question(side stream)`
@@ -570,10 +594,7 @@ static int forward_words_impl(qmann_model *m, const uint16_t *story_words, uint3
         [&](void *s) { return qmann_embed_query_idx(&m->net, question_words, max_q_words, m->t_q, m->u0, n_query, s); },
         !top);                                              // (the top call's hop launch is never split by story length)
     if (rc) return rc;
-    rc = hops_and_answer(m, rows_total, row_off, max_slots, n_query, answer, pred, cost, match, stream, split_ws, top);
-    if (!rc) rc = qm_scope.rc();
-    if (!rc) m->last_n_query = n_query;
-    return rc;
+    return hops_and_answer(m, qm_scope, rows_total, row_off, max_slots, n_query, answer, pred, cost, match, stream, split_ws, top);
 }
 
 int qmann_model_forward_words(qmann_model *m, const uint16_t *story_words, uint32_t rows_total, uint32_t max_words,
@@ -590,8 +611,7 @@ int qmann_model_forward_words_top(qmann_model *m, const uint16_t *story_words, u
                                   uint32_t max_slots, uint32_t n_query, const uint32_t *answer, uint32_t *pred,
                                   float *cost, uint32_t *match, uint32_t k, uint32_t *top_slot, float *top_p, void *stream)
 {
-    QmHopHints top;
-    top.top_on = true; top.top_k = k; top.top_slot = top_slot; top.top_p = top_p;
+    const QmHopHints top = top_hints(false, k, top_slot, top_p);
     return forward_words_impl(m, story_words, rows_total, max_words, question_words, max_q_words, row_off, max_slots, n_query,
                               answer, pred, cost, match, stream, &top);
 }
@@ -601,8 +621,7 @@ int qmann_model_forward_words_top_float(qmann_model *m, const uint16_t *story_wo
                                         uint32_t max_slots, uint32_t n_query, const uint32_t *answer, uint32_t *pred,
                                         float *cost, uint32_t *match, uint32_t k, uint32_t *top_slot, float *top_p, void *stream)
 {
-    QmHopHints top;
-    top.top_on = top.top_float = true; top.top_k = k; top.top_slot = top_slot; top.top_p = top_p;
+    const QmHopHints top = top_hints(true, k, top_slot, top_p);
     return forward_words_impl(m, story_words, rows_total, max_words, question_words, max_q_words, row_off, max_slots, n_query,
                               answer, pred, cost, match, stream, &top);
 }
@@ -629,10 +648,7 @@ int qmann_model_forward_shared_words(qmann_model *m, const uint16_t *story_words
     if (rc) return rc;
     rc = qmann_hops_shared_i8(&m->net, m->keys, m->vals, m->tied ? 0 : plane, n_rows, m->u0, m->u, nullptr, n_query, stream);
     if (rc) return rc;
-    rc = qmann_answer_f32(&m->net, m->w_ans, m->u, answer, pred, nullptr, cost, match, n_query, stream);
-    if (!rc) rc = qm_scope.rc();
-    if (!rc) m->last_n_query = n_query;
-    return rc;
+    return answer_and_finish(m, qm_scope, false, n_query, answer, pred, cost, match, stream);     // (this call has always ignored answer_exact)
 }
 
 int qmann_model_memorize_words(qmann_model *m, const uint16_t *story_words, uint32_t n_rows, uint32_t max_words, void *stream)
@@ -648,7 +664,7 @@ int qmann_model_memorize_words(qmann_model *m, const uint16_t *story_words, uint
     // the memory's length against LDS now, so that an ask cannot fail late
     const size_t lds = ask_lds_bytes(m, n_rows);
     // (with split asks enabled a memory may be longer: then one query's share of the workspace must fit the budget)
-    if (lds > kAskLdsLimit && !(n_rows <= (1u << 24) && ask_splits(m, n_rows, 1))) return QMANN_ERANGE;
+    if (lds > kHopLdsLimit && !(n_rows <= (1u << 24) && ask_splits(m, n_rows, 1))) return QMANN_ERANGE;
     DeviceScope on(m->device);
     m->mem_rows = 0;                                         // (a failure below leaves nothing memorised)
     const size_t n_plane = m->tied ? 1 : m->H;
@@ -699,45 +715,43 @@ static int ask_words_impl(qmann_model *m, const uint16_t *question_words, uint32
     const size_t plane = m->tied ? 0 : (size_t)S * m->Dp;
     rc = qmann_embed_query_idx(&m->net, question_words, max_q_words, m->t_q, m->u0, n_query, stream);
     if (rc) return rc;
-    const bool packed = packed_mode(m->net);
+    const qmann_net *net = &m->net;
+    const bool packed = packed_mode(m->net), fl = net->attention_mode == QMANN_ATT_FLOAT;
     const size_t key_plane = plane / m->Dp * (m->Dp / 64) * m->net.num_bit * 8;     // (packed: bytes of one hop's key planes)
-    if (ask_splits(m, S, n_query)) {
-        // chunks of as many questions as the workspace holds, one after the other on the caller's stream
-        const size_t fit = m->split_bytes / ask_split_share(m, S);
-        const uint32_t chunk = fit < n_query ? (uint32_t)fit : n_query;
-        for (uint32_t q0 = 0; q0 < n_query && !rc; q0 += chunk) {
-            const uint32_t nq = n_query - q0 < chunk ? n_query - q0 : chunk;
-            const float *u0 = m->u0 + (size_t)q0 * m->D;
-            float *u = m->u + (size_t)q0 * m->D;
-            const size_t row0 = (size_t)q0 * m->H * k;     // (top: the chunk's own block of rows)
-            rc = packed && top ? qmann_hops_shared_split_top_packed(&m->net, m->mem_planes, key_plane, m->mem_vals, plane, S, u0, u, k,
-                                                                    top_slot + row0, top_p + row0, nq, 0, m->split_ws,
-                                                                    m->split_bytes, stream)
-                 : packed ? qmann_hops_shared_split_packed(&m->net, m->mem_planes, key_plane, m->mem_vals, plane, S, u0, u, nullptr, nq, 0,
-                                                         m->split_ws, m->split_bytes, stream)
-                 : top  ? qmann_hops_shared_split_top_i8(&m->net, m->mem_keys, m->mem_vals, plane, S, u0, u, k, top_slot + row0,
-                                                         top_p + row0, nq, 0, m->split_ws, m->split_bytes, stream)
-                        : qmann_hops_shared_split_i8(&m->net, m->mem_keys, m->mem_vals, plane, S, u0, u, nullptr, nq, 0, m->split_ws,
-                                                     m->split_bytes, stream);
+    // Float models never split: both enable calls refuse them, so they have no workspace -- and no split call exists to pick.
+    const bool split = !fl && ask_splits(m, S, n_query);
+    // THE place that picks an ask's hop call -- by family (float, packed, fixed-point), top and split -- for questions q0 .. q0 + nq
+    auto hops = [&](uint32_t q0, uint32_t nq) {
+        const float *u0 = m->u0 + (size_t)q0 * m->D;
+        float *u = m->u + (size_t)q0 * m->D;
+        const size_t row0 = (size_t)q0 * m->H * k;         // (top: the chunk's own block of rows)
+        uint32_t *ts = top_slot + row0;
+        float *tp = top_p + row0;
+        void *ws = m->split_ws;
+        const size_t wb = m->split_bytes;
+        if (fl)
+            return top ? qmann_hops_shared_top_float_i8(net, m->mem_keys, m->mem_vals, plane, S, u0, u, k, ts, tp, nq, stream)
+                       : qmann_hops_shared_float_i8(net, m->mem_keys, m->mem_vals, plane, S, u0, u, nullptr, nq, stream);
+        if (packed) {
+            if (split)
+                return top ? qmann_hops_shared_split_top_packed(net, m->mem_planes, key_plane, m->mem_vals, plane, S, u0, u, k, ts, tp, nq, 0, ws, wb, stream)
+                           : qmann_hops_shared_split_packed(net, m->mem_planes, key_plane, m->mem_vals, plane, S, u0, u, nullptr, nq, 0, ws, wb, stream);
+            return top ? qmann_hops_shared_top_packed(net, m->mem_planes, key_plane, m->mem_vals, plane, S, u0, u, k, ts, tp, nq, stream)
+                       : qmann_hops_shared_packed(net, m->mem_planes, key_plane, m->mem_vals, plane, S, u0, u, nullptr, nq, stream);
         }
-    } else if (top == kAskTopFloat)
-        rc = qmann_hops_shared_top_float_i8(&m->net, m->mem_keys, m->mem_vals, plane, S, m->u0, m->u, k, top_slot, top_p, n_query, stream);
-    else if (m->net.attention_mode == QMANN_ATT_FLOAT)
-        rc = qmann_hops_shared_float_i8(&m->net, m->mem_keys, m->mem_vals, plane, S, m->u0, m->u, nullptr, n_query, stream);
-    else if (packed && top)
-        rc = qmann_hops_shared_top_packed(&m->net, m->mem_planes, key_plane, m->mem_vals, plane, S, m->u0, m->u, k, top_slot, top_p,
-                                          n_query, stream);
-    else if (packed)
-        rc = qmann_hops_shared_packed(&m->net, m->mem_planes, key_plane, m->mem_vals, plane, S, m->u0, m->u, nullptr, n_query, stream);
-    else if (top)
-        rc = qmann_hops_shared_top_i8(&m->net, m->mem_keys, m->mem_vals, plane, S, m->u0, m->u, k, top_slot, top_p, n_query, stream);
-    else
-        rc = qmann_hops_shared_i8(&m->net, m->mem_keys, m->mem_vals, plane, S, m->u0, m->u, nullptr, n_query, stream);
+        if (split)
+            return top ? qmann_hops_shared_split_top_i8(net, m->mem_keys, m->mem_vals, plane, S, u0, u, k, ts, tp, nq, 0, ws, wb, stream)
+                       : qmann_hops_shared_split_i8(net, m->mem_keys, m->mem_vals, plane, S, u0, u, nullptr, nq, 0, ws, wb, stream);
+        return top ? qmann_hops_shared_top_i8(net, m->mem_keys, m->mem_vals, plane, S, u0, u, k, ts, tp, nq, stream)
+                   : qmann_hops_shared_i8(net, m->mem_keys, m->mem_vals, plane, S, u0, u, nullptr, nq, stream);
+    };
+    // A split ask: chunks of as many questions as the workspace holds, one after the other on the caller's stream.  An unsplit
+    // ask: the same loop with one chunk of all of them.
+    const size_t fit = split ? m->split_bytes / ask_split_share(m, S) : n_query;
+    const uint32_t chunk = fit < n_query ? (uint32_t)fit : n_query;
+    for (uint32_t q0 = 0; q0 < n_query && !rc; q0 += chunk) rc = hops(q0, n_query - q0 < chunk ? n_query - q0 : chunk);
     if (rc) return rc;
-    rc = (m->answer_exact ? qmann_answer_f32_serial : qmann_answer_f32)(&m->net, m->w_ans, m->u, answer, pred, nullptr, cost, match, n_query, stream);
-    if (!rc) rc = qm_scope.rc();
-    if (!rc) m->last_n_query = n_query;
-    return rc;
+    return answer_and_finish(m, qm_scope, m->answer_exact, n_query, answer, pred, cost, match, stream);
 }
 
 int qmann_model_ask_words(qmann_model *m, const uint16_t *question_words, uint32_t max_q_words, uint32_t n_query,
@@ -771,12 +785,7 @@ uint32_t qmann_model_memory_rows(const qmann_model *m) { return m ? m->mem_rows 
 
 int qmann_model_enable_split_asks(qmann_model *m, size_t scratch_bytes, void *stream)
 {
-    QmBatched qm_scope;
-    if (!m) return QMANN_EINVAL;
-    if (m->net.attention_mode != QMANN_ATT_FIXED) return QMANN_EUNSUPPORTED;
-    DeviceScope on(m->device);
-    const int rc = set_split_workspace(m, scratch_bytes, stream);
-    return rc ? rc : qm_scope.rc();
+    return enable_split_asks(m, [](const qmann_model *x) { return x->net.attention_mode == QMANN_ATT_FIXED; }, scratch_bytes, stream);
 }
 
 int qmann_model_enable_float_asks(qmann_model *m, int on)
@@ -790,12 +799,7 @@ int qmann_model_enable_float_asks(qmann_model *m, int on)
 
 int qmann_model_enable_split_asks_packed(qmann_model *m, size_t scratch_bytes, void *stream)
 {
-    QmBatched qm_scope;
-    if (!m) return QMANN_EINVAL;
-    if (!packed_model_ok(m)) return QMANN_EUNSUPPORTED;
-    DeviceScope on(m->device);
-    const int rc = set_split_workspace(m, scratch_bytes, stream);
-    return rc ? rc : qm_scope.rc();
+    return enable_split_asks(m, packed_model_ok, scratch_bytes, stream);
 }
 
 int qmann_model_forward_bow(qmann_model *m, const float *story, uint32_t rows_total, const float *question,
@@ -846,10 +850,7 @@ int qmann_model_forward_bow(qmann_model *m, const float *story, uint32_t rows_to
             return e ? e : qmann_embed_query_rows(&m->net, question, irr_q, n_irr + 1, m->w_q, m->u0, n_query, s);
         });
     if (rc) return rc;
-    rc = hops_and_answer(m, rows_total, row_off, max_slots, n_query, answer, pred, cost, match, stream, split_ws);
-    if (!rc) rc = qm_scope.rc();
-    if (!rc) m->last_n_query = n_query;
-    return rc;
+    return hops_and_answer(m, qm_scope, rows_total, row_off, max_slots, n_query, answer, pred, cost, match, stream, split_ws);
 }
 
 const float *qmann_model_last_u(const qmann_model *m) { return m ? m->u : nullptr; }

@@ -141,6 +141,9 @@ static inline bool qm_too_many_queries(uint32_t n_query) { return n_query >= (1u
 // ---- launches -------------------------------------------------------------------------------------------------------------
 // dynamic LDS a kernel may use without hipFuncSetAttribute (static arrays come on top, hence the margin)
 constexpr size_t kLdsDefaultLimit = 48 * 1024;
+// dynamic LDS a hop launch may take (a CU has 160 KiB; a little static LDS is used besides).  ONE value for every hop entry
+// point's QMANN_ERANGE and for the host model (model_host.hip), which refuses a memory ahead of the ask that would.
+constexpr size_t kHopLdsLimit = 160 * 1024 - 1024;
 
 // One launch: beyond the default limit the kernel's dynamic-LDS limit is raised first (no cached state: thread- and
 // device-safe).  The caller checks the launch (QM_LAUNCH_CHECK).

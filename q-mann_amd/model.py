@@ -140,6 +140,16 @@ def _zero_cost_and_match(dev):
     return acc[:1].view(torch.float32), acc[1:]
 
 
+def _words(t):
+    """a story's word-index array [rows][W] as the model calls take it: pointer, rows, W"""
+    return _ptr(t), t.shape[0], t.shape[1]
+
+
+def _qwords(t):
+    """the questions' word-index array [B][Wq] as the model calls take it: pointer, Wq (B follows later in the call)"""
+    return _ptr(t), t.shape[1]
+
+
 def _top_out(dev, B, H, k):
     """outputs of the attended-slots calls: top_slot int32 [B][H][k] (0xFFFFFFFF reads -1), top_p float32 [B][H][k]"""
     if not 1 <= k <= abi.QMANN_MAX_TOP_SLOTS:
@@ -204,6 +214,64 @@ class QNet:
                   "qmann_quantize_i8")
         return out
 
+    def _taps(self, B, *slots):
+        """the taps of a hop call and their abi.Taps: score_codes / scores / probs [H][*slots] -- [rows] where every query has
+        its own story, [B][n_slots] on one shared memory -- and o / u [B][H][D]"""
+        def z(shape, dtype=torch.float32):
+            return torch.zeros(shape, dtype=dtype, device=self.dev)
+        t = HopTaps(z((self.H, *slots), torch.int32), z((self.H, *slots)), z((self.H, *slots)),
+                    z((B, self.H, self.D)), z((B, self.H, self.D)))
+        return t, abi.Taps(t.score_codes.data_ptr(), t.scores.data_ptr(), t.probs.data_ptr(), t.o.data_ptr(), t.u.data_ptr())
+
+    def _i8_planes(self, keys, vals, rows, *lengths):
+        """int8 memories keys/vals [H][rows][Dp], or [1][rows][Dp] for tied hops, checked, as the hop calls take them: keys,
+        vals, hop stride, then the call's own lengths (row_off and max_slots, or n_slots)"""
+        assert keys.shape in ((self.H, rows, self.Dp), (1, rows, self.Dp)) and vals.shape == keys.shape
+        assert keys.is_contiguous() and vals.is_contiguous()
+        hop_stride = rows * self.Dp if keys.shape[0] == self.H else 0             # one plane for several hops: tied
+        return (_ptr(keys), _ptr(vals), hop_stride, *lengths)
+
+    def _packed_planes(self, key_planes, vals, n_slots):
+        """a packed shared memory (key_planes int64 [H or 1][n_slots][Dp/64][num_bit], vals int8 [H or 1][n_slots][Dp]), checked,
+        as the hop calls take it: key planes, key stride, vals, value stride, n_slots"""
+        nb = key_planes.shape[-1]
+        assert vals.shape in ((self.H, n_slots, self.Dp), (1, n_slots, self.Dp))
+        assert key_planes.shape == (vals.shape[0], n_slots, self.Dp // 64, nb)
+        assert key_planes.is_contiguous() and vals.is_contiguous()
+        per_hop = vals.shape[0] == self.H
+        key_stride = n_slots * (self.Dp // 64) * nb * 8 if per_hop else 0         # one plane for several hops: tied
+        val_stride = n_slots * self.Dp if per_hop else 0
+        return (_ptr(key_planes), key_stride, _ptr(vals), val_stride, n_slots)
+
+    def _split_workspace(self, size_fn, n_slots, B, ws=None):
+        """the last arguments of a slot-split call but n_slices: (ws, nbytes), nbytes as the library's helper gives them, ws
+        allocated here unless given"""
+        nbytes = int(size_fn(C.byref(self.net), n_slots, B))
+        if ws is None:
+            ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=self.dev)   # (torch allocations are 16-byte aligned)
+        return ws, nbytes
+
+    def _hops_top(self, name, planes, u0, k, split=()):
+        """an attended-slots call, `name`(net, *planes, u0, u_out, k, top_slot, top_p, B, *split, stream) -> (u_out, top_slot,
+        top_p).  planes: _i8_planes or _packed_planes; split: n_slices, ws, nbytes of a slot-split call"""
+        B = u0.shape[0]
+        u_out = torch.empty_like(u0)
+        top_slot, top_p = _top_out(self.dev, B, self.H, k)
+        abi.check(getattr(abi.lib, name)(C.byref(self.net), *planes, _ptr(u0), _ptr(u_out), k, _ptr(top_slot), _ptr(top_p), B,
+                                         *split, self._s()), name)
+        return u_out, top_slot, top_p
+
+    def _hops_shared(self, name, planes, n_slots, u0, taps, u_out=None, split=()):
+        """a shared-plane call with optional taps, `name`(net, *planes, u0, u_out, taps, B, *split, stream) -> u_out, or
+        (u_out, HopTaps).  planes and split as _hops_top takes them"""
+        B = u0.shape[0]
+        if u_out is None:
+            u_out = torch.empty_like(u0)
+        tobj, tp = self._taps(B, B, n_slots) if taps else (None, None)
+        abi.check(getattr(abi.lib, name)(C.byref(self.net), *planes, _ptr(u0), _ptr(u_out), C.byref(tp) if tp else None, B,
+                                         *split, self._s()), name)
+        return (u_out, tobj) if taps else u_out
+
     # ---- stages --------------------------------------------------------------------------
     def embed(self, story: torch.Tensor, question: torch.Tensor):
         """story [rows_total][V] float, question [B][V] float -> keys, vals int8 [H][rows][Dp], u0 [B][D]."""
@@ -253,16 +321,7 @@ class QNet:
         assert keys.shape == (self.H, rows, self.Dp) and keys.is_contiguous() and vals.is_contiguous()
         if u_out is None:
             u_out = torch.empty_like(u0)
-        tp, tobj = None, None
-        if taps:
-            tobj = HopTaps(
-                torch.zeros((self.H, rows), dtype=torch.int32, device=self.dev),
-                torch.zeros((self.H, rows), dtype=torch.float32, device=self.dev),
-                torch.zeros((self.H, rows), dtype=torch.float32, device=self.dev),
-                torch.zeros((B, self.H, self.D), dtype=torch.float32, device=self.dev),
-                torch.zeros((B, self.H, self.D), dtype=torch.float32, device=self.dev))
-            tp = abi.Taps(tobj.score_codes.data_ptr(), tobj.scores.data_ptr(), tobj.probs.data_ptr(),
-                          tobj.o.data_ptr(), tobj.u.data_ptr())
+        tobj, tp = self._taps(B, rows) if taps else (None, None)
         abi.check(abi.lib.qmann_hops_i8(C.byref(self.net), _ptr(keys), _ptr(vals), rows * self.Dp, _ptr(row_off),
                                         max_slots, _ptr(u0), _ptr(u_out), C.byref(tp) if tp else None, B,
                                         self._s()), "qmann_hops_i8")
@@ -274,155 +333,57 @@ class QNet:
         the story's first row, larger probability first, equal probabilities: lower slot first; entries past the story's
         length (cut to max_slots) are slot -1 (0xFFFFFFFF), p 0.  keys/vals int8 [H][rows][Dp], or [1][rows][Dp] for tied hops
         (hop stride 0); the other arguments as hops."""
-        B = u0.shape[0]
-        rows = keys.shape[1]
-        assert keys.shape in ((self.H, rows, self.Dp), (1, rows, self.Dp)) and vals.shape == keys.shape
-        assert keys.is_contiguous() and vals.is_contiguous()
-        u_out = torch.empty_like(u0)
-        top_slot, top_p = _top_out(self.dev, B, self.H, k)
-        hop_stride = rows * self.Dp if keys.shape[0] == self.H else 0             # one plane for several hops: tied
-        abi.check(abi.lib.qmann_hops_top_i8(C.byref(self.net), _ptr(keys), _ptr(vals), hop_stride, _ptr(row_off), max_slots,
-                                            _ptr(u0), _ptr(u_out), k, _ptr(top_slot), _ptr(top_p), B, self._s()),
-                  "qmann_hops_top_i8")
-        return u_out, top_slot, top_p
+        planes = self._i8_planes(keys, vals, keys.shape[1], _ptr(row_off), max_slots)
+        return self._hops_top("qmann_hops_top_i8", planes, u0, k)
 
     def hops_top_float(self, keys, vals, row_off, max_slots, u0, k):
         """qmann_hops_top_float_i8: hops_top for float attention (attention_mode 1), at every story length hops takes in that
         mode: (u_out, top_slot int32 [B][H][k], top_p float32 [B][H][k]); arguments and padding as hops_top."""
-        B = u0.shape[0]
-        rows = keys.shape[1]
-        assert keys.shape in ((self.H, rows, self.Dp), (1, rows, self.Dp)) and vals.shape == keys.shape
-        assert keys.is_contiguous() and vals.is_contiguous()
-        u_out = torch.empty_like(u0)
-        top_slot, top_p = _top_out(self.dev, B, self.H, k)
-        hop_stride = rows * self.Dp if keys.shape[0] == self.H else 0             # one plane for several hops: tied
-        abi.check(abi.lib.qmann_hops_top_float_i8(C.byref(self.net), _ptr(keys), _ptr(vals), hop_stride, _ptr(row_off), max_slots,
-                                                  _ptr(u0), _ptr(u_out), k, _ptr(top_slot), _ptr(top_p), B, self._s()),
-                  "qmann_hops_top_float_i8")
-        return u_out, top_slot, top_p
+        planes = self._i8_planes(keys, vals, keys.shape[1], _ptr(row_off), max_slots)
+        return self._hops_top("qmann_hops_top_float_i8", planes, u0, k)
 
     def hops_shared_top_float(self, keys, vals, n_slots, u0, k):
         """qmann_hops_shared_top_float_i8: hops_shared_float plus, per query and hop, the k most attended slots of the one
         memory and their probabilities: (u_out, top_slot int32 [B][H][k], top_p float32 [B][H][k]), larger probability first,
         equal probabilities: lower slot first; entries past n_slots are slot -1 (0xFFFFFFFF), p 0."""
-        B = u0.shape[0]
-        assert keys.shape in ((self.H, n_slots, self.Dp), (1, n_slots, self.Dp)) and vals.shape == keys.shape
-        assert keys.is_contiguous() and vals.is_contiguous()
-        u_out = torch.empty_like(u0)
-        top_slot, top_p = _top_out(self.dev, B, self.H, k)
-        hop_stride = n_slots * self.Dp if keys.shape[0] == self.H else 0          # one plane for several hops: tied
-        abi.check(abi.lib.qmann_hops_shared_top_float_i8(C.byref(self.net), _ptr(keys), _ptr(vals), hop_stride, n_slots, _ptr(u0),
-                                                         _ptr(u_out), k, _ptr(top_slot), _ptr(top_p), B, self._s()),
-                  "qmann_hops_shared_top_float_i8")
-        return u_out, top_slot, top_p
+        return self._hops_top("qmann_hops_shared_top_float_i8", self._i8_planes(keys, vals, n_slots, n_slots), u0, k)
 
     def hops_shared(self, keys, vals, n_slots, u0, taps=False, u_out=None):
         """qmann_hops_shared_i8: ONE memory for every query.  keys/vals int8 [H][n_slots][Dp], or [1][n_slots][Dp] for tied
         hops (hop stride 0); u0 [B][D] float.  taps: score_codes / scores / probs [H][B][n_slots], o / u [B][H][D]."""
-        B = u0.shape[0]
-        assert keys.shape in ((self.H, n_slots, self.Dp), (1, n_slots, self.Dp)) and vals.shape == keys.shape
-        assert keys.is_contiguous() and vals.is_contiguous()
-        if u_out is None:
-            u_out = torch.empty_like(u0)
-        tp, tobj = None, None
-        if taps:
-            tobj = HopTaps(
-                torch.zeros((self.H, B, n_slots), dtype=torch.int32, device=self.dev),
-                torch.zeros((self.H, B, n_slots), dtype=torch.float32, device=self.dev),
-                torch.zeros((self.H, B, n_slots), dtype=torch.float32, device=self.dev),
-                torch.zeros((B, self.H, self.D), dtype=torch.float32, device=self.dev),
-                torch.zeros((B, self.H, self.D), dtype=torch.float32, device=self.dev))
-            tp = abi.Taps(tobj.score_codes.data_ptr(), tobj.scores.data_ptr(), tobj.probs.data_ptr(),
-                          tobj.o.data_ptr(), tobj.u.data_ptr())
-        hop_stride = n_slots * self.Dp if keys.shape[0] == self.H else 0          # one plane for several hops: tied
-        abi.check(abi.lib.qmann_hops_shared_i8(C.byref(self.net), _ptr(keys), _ptr(vals), hop_stride, n_slots, _ptr(u0),
-                                               _ptr(u_out), C.byref(tp) if tp else None, B, self._s()),
-                  "qmann_hops_shared_i8")
-        return (u_out, tobj) if taps else u_out
+        planes = self._i8_planes(keys, vals, n_slots, n_slots)
+        return self._hops_shared("qmann_hops_shared_i8", planes, n_slots, u0, taps, u_out)
 
     def hops_shared_float(self, keys, vals, n_slots, u0, taps=False, u_out=None):
         """qmann_hops_shared_float_i8: hops_shared for float attention (attention_mode 1).  keys/vals int8 [H][n_slots][Dp], or
         [1][n_slots][Dp] for tied hops (hop stride 0), on the weight grid; u0 [B][D] float.  taps: score_codes / scores / probs
         [H][B][n_slots], o / u [B][H][D]."""
-        B = u0.shape[0]
-        assert keys.shape in ((self.H, n_slots, self.Dp), (1, n_slots, self.Dp)) and vals.shape == keys.shape
-        assert keys.is_contiguous() and vals.is_contiguous()
-        if u_out is None:
-            u_out = torch.empty_like(u0)
-        tp, tobj = None, None
-        if taps:
-            tobj = HopTaps(
-                torch.zeros((self.H, B, n_slots), dtype=torch.int32, device=self.dev),
-                torch.zeros((self.H, B, n_slots), dtype=torch.float32, device=self.dev),
-                torch.zeros((self.H, B, n_slots), dtype=torch.float32, device=self.dev),
-                torch.zeros((B, self.H, self.D), dtype=torch.float32, device=self.dev),
-                torch.zeros((B, self.H, self.D), dtype=torch.float32, device=self.dev))
-            tp = abi.Taps(tobj.score_codes.data_ptr(), tobj.scores.data_ptr(), tobj.probs.data_ptr(),
-                          tobj.o.data_ptr(), tobj.u.data_ptr())
-        hop_stride = n_slots * self.Dp if keys.shape[0] == self.H else 0          # one plane for several hops: tied
-        abi.check(abi.lib.qmann_hops_shared_float_i8(C.byref(self.net), _ptr(keys), _ptr(vals), hop_stride, n_slots, _ptr(u0),
-                                                     _ptr(u_out), C.byref(tp) if tp else None, B, self._s()),
-                  "qmann_hops_shared_float_i8")
-        return (u_out, tobj) if taps else u_out
+        planes = self._i8_planes(keys, vals, n_slots, n_slots)
+        return self._hops_shared("qmann_hops_shared_float_i8", planes, n_slots, u0, taps, u_out)
 
     def hops_shared_split(self, keys, vals, n_slots, u0, n_slices=0, taps=False, u_out=None):
         """qmann_hops_shared_split_i8: hops_shared with the slots cut into n_slices slices (0: the library's choice); the
         workspace is allocated here, of the size the library's helper gives.  Arguments, results and taps as hops_shared."""
-        B = u0.shape[0]
-        assert keys.shape in ((self.H, n_slots, self.Dp), (1, n_slots, self.Dp)) and vals.shape == keys.shape
-        assert keys.is_contiguous() and vals.is_contiguous()
-        if u_out is None:
-            u_out = torch.empty_like(u0)
-        tp, tobj = None, None
-        if taps:
-            tobj = HopTaps(
-                torch.zeros((self.H, B, n_slots), dtype=torch.int32, device=self.dev),
-                torch.zeros((self.H, B, n_slots), dtype=torch.float32, device=self.dev),
-                torch.zeros((self.H, B, n_slots), dtype=torch.float32, device=self.dev),
-                torch.zeros((B, self.H, self.D), dtype=torch.float32, device=self.dev),
-                torch.zeros((B, self.H, self.D), dtype=torch.float32, device=self.dev))
-            tp = abi.Taps(tobj.score_codes.data_ptr(), tobj.scores.data_ptr(), tobj.probs.data_ptr(),
-                          tobj.o.data_ptr(), tobj.u.data_ptr())
-        nbytes = int(abi.lib.qmann_hops_shared_split_ws_bytes(C.byref(self.net), n_slots, B))
-        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=self.dev)       # (torch allocations are 16-byte aligned)
-        hop_stride = n_slots * self.Dp if keys.shape[0] == self.H else 0          # one plane for several hops: tied
-        abi.check(abi.lib.qmann_hops_shared_split_i8(C.byref(self.net), _ptr(keys), _ptr(vals), hop_stride, n_slots, _ptr(u0),
-                                                     _ptr(u_out), C.byref(tp) if tp else None, B, n_slices, _ptr(ws), nbytes,
-                                                     self._s()), "qmann_hops_shared_split_i8")
+        planes = self._i8_planes(keys, vals, n_slots, n_slots)
+        ws, nbytes = self._split_workspace(abi.lib.qmann_hops_shared_split_ws_bytes, n_slots, u0.shape[0])
+        r = self._hops_shared("qmann_hops_shared_split_i8", planes, n_slots, u0, taps, u_out, (n_slices, _ptr(ws), nbytes))
         self._split_ws = ws                                                       # alive until the next call: the launch is asynchronous
-        return (u_out, tobj) if taps else u_out
+        return r
 
     def hops_shared_top(self, keys, vals, n_slots, u0, k):
         """qmann_hops_shared_top_i8: hops_shared plus, per query and hop, the k most attended slots and their probabilities:
         (u_out, top_slot int32 [B][H][k], top_p float32 [B][H][k]), larger probability first, equal probabilities: lower slot
         first; entries past n_slots are slot -1 (0xFFFFFFFF), p 0.  Arguments as hops_shared."""
-        B = u0.shape[0]
-        assert keys.shape in ((self.H, n_slots, self.Dp), (1, n_slots, self.Dp)) and vals.shape == keys.shape
-        assert keys.is_contiguous() and vals.is_contiguous()
-        u_out = torch.empty_like(u0)
-        top_slot, top_p = _top_out(self.dev, B, self.H, k)
-        hop_stride = n_slots * self.Dp if keys.shape[0] == self.H else 0          # one plane for several hops: tied
-        abi.check(abi.lib.qmann_hops_shared_top_i8(C.byref(self.net), _ptr(keys), _ptr(vals), hop_stride, n_slots, _ptr(u0),
-                                                   _ptr(u_out), k, _ptr(top_slot), _ptr(top_p), B, self._s()),
-                  "qmann_hops_shared_top_i8")
-        return u_out, top_slot, top_p
+        return self._hops_top("qmann_hops_shared_top_i8", self._i8_planes(keys, vals, n_slots, n_slots), u0, k)
 
     def hops_shared_split_top(self, keys, vals, n_slots, u0, k, n_slices=0):
         """qmann_hops_shared_split_top_i8: hops_shared_top with the slots cut into n_slices slices (0: the library's choice);
         the workspace is allocated here, of the size hops_shared_split takes.  Results as hops_shared_top."""
-        B = u0.shape[0]
-        assert keys.shape in ((self.H, n_slots, self.Dp), (1, n_slots, self.Dp)) and vals.shape == keys.shape
-        assert keys.is_contiguous() and vals.is_contiguous()
-        u_out = torch.empty_like(u0)
-        top_slot, top_p = _top_out(self.dev, B, self.H, k)
-        nbytes = int(abi.lib.qmann_hops_shared_split_ws_bytes(C.byref(self.net), n_slots, B))
-        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=self.dev)       # (torch allocations are 16-byte aligned)
-        hop_stride = n_slots * self.Dp if keys.shape[0] == self.H else 0
-        abi.check(abi.lib.qmann_hops_shared_split_top_i8(C.byref(self.net), _ptr(keys), _ptr(vals), hop_stride, n_slots, _ptr(u0),
-                                                         _ptr(u_out), k, _ptr(top_slot), _ptr(top_p), B, n_slices, _ptr(ws),
-                                                         nbytes, self._s()), "qmann_hops_shared_split_top_i8")
+        planes = self._i8_planes(keys, vals, n_slots, n_slots)
+        ws, nbytes = self._split_workspace(abi.lib.qmann_hops_shared_split_ws_bytes, n_slots, u0.shape[0])
+        r = self._hops_top("qmann_hops_shared_split_top_i8", planes, u0, k, (n_slices, _ptr(ws), nbytes))
         self._split_ws = ws                                                       # alive until the next call: the launch is asynchronous
-        return u_out, top_slot, top_p
+        return r
 
     def pack_planes(self, sm_codes: torch.Tensor, num_bit: int) -> torch.Tensor:
         """sign-magnitude int8 [..., rows, Dp] -> packed bit planes int64 [..., rows, Dp/64, num_bit]."""
@@ -439,16 +400,7 @@ class QNet:
         rows = vals.shape[1]
         nb = key_planes.shape[-1]
         u_out = torch.empty_like(u0)
-        tp, tobj = None, None
-        if taps:
-            tobj = HopTaps(
-                torch.zeros((self.H, rows), dtype=torch.int32, device=self.dev),
-                torch.zeros((self.H, rows), dtype=torch.float32, device=self.dev),
-                torch.zeros((self.H, rows), dtype=torch.float32, device=self.dev),
-                torch.zeros((B, self.H, self.D), dtype=torch.float32, device=self.dev),
-                torch.zeros((B, self.H, self.D), dtype=torch.float32, device=self.dev))
-            tp = abi.Taps(tobj.score_codes.data_ptr(), tobj.scores.data_ptr(), tobj.probs.data_ptr(),
-                          tobj.o.data_ptr(), tobj.u.data_ptr())
+        tobj, tp = self._taps(B, rows) if taps else (None, None)
         abi.check(abi.lib.qmann_hops_packed(C.byref(self.net), _ptr(key_planes), rows * (self.Dp // 64) * nb * 8,
                                             _ptr(vals), rows * self.Dp, _ptr(row_off), max_slots, _ptr(u0),
                                             _ptr(u_out), C.byref(tp) if tp else None, B, self._s()),
@@ -459,103 +411,32 @@ class QNet:
         """qmann_hops_shared_packed: Hamming V0 / V1 attention on ONE memory for every query.  key_planes int64
         [H or 1][n_slots][Dp/64][num_bit], vals int8 [H or 1][n_slots][Dp] (1: tied hops, both strides 0); u0 [B][D] float.
         taps: score_codes / scores / probs [H][B][n_slots], o / u [B][H][D]."""
-        B = u0.shape[0]
-        nb = key_planes.shape[-1]
-        assert vals.shape in ((self.H, n_slots, self.Dp), (1, n_slots, self.Dp))
-        assert key_planes.shape == (vals.shape[0], n_slots, self.Dp // 64, nb)
-        assert key_planes.is_contiguous() and vals.is_contiguous()
-        u_out = torch.empty_like(u0)
-        tp, tobj = None, None
-        if taps:
-            tobj = HopTaps(
-                torch.zeros((self.H, B, n_slots), dtype=torch.int32, device=self.dev),
-                torch.zeros((self.H, B, n_slots), dtype=torch.float32, device=self.dev),
-                torch.zeros((self.H, B, n_slots), dtype=torch.float32, device=self.dev),
-                torch.zeros((B, self.H, self.D), dtype=torch.float32, device=self.dev),
-                torch.zeros((B, self.H, self.D), dtype=torch.float32, device=self.dev))
-            tp = abi.Taps(tobj.score_codes.data_ptr(), tobj.scores.data_ptr(), tobj.probs.data_ptr(),
-                          tobj.o.data_ptr(), tobj.u.data_ptr())
-        per_hop = vals.shape[0] == self.H
-        key_stride = n_slots * (self.Dp // 64) * nb * 8 if per_hop else 0         # one plane for several hops: tied
-        val_stride = n_slots * self.Dp if per_hop else 0
-        abi.check(abi.lib.qmann_hops_shared_packed(C.byref(self.net), _ptr(key_planes), key_stride, _ptr(vals), val_stride,
-                                                   n_slots, _ptr(u0), _ptr(u_out), C.byref(tp) if tp else None, B, self._s()),
-                  "qmann_hops_shared_packed")
-        return (u_out, tobj) if taps else u_out
+        return self._hops_shared("qmann_hops_shared_packed", self._packed_planes(key_planes, vals, n_slots), n_slots, u0, taps)
 
     def hops_shared_split_packed(self, key_planes, vals, n_slots, u0, n_slices=0, taps=False, u_out=None, ws=None):
         """qmann_hops_shared_split_packed: hops_shared_packed with the slots cut into n_slices slices (0: the library's choice).
         ws: a uint8 workspace of the caller's (16-byte aligned, at least the helper's size); None: allocated here, of the size
         the library's helper gives.  Arguments, results and taps as hops_shared_packed."""
-        B = u0.shape[0]
-        nb = key_planes.shape[-1]
-        assert vals.shape in ((self.H, n_slots, self.Dp), (1, n_slots, self.Dp))
-        assert key_planes.shape == (vals.shape[0], n_slots, self.Dp // 64, nb)
-        assert key_planes.is_contiguous() and vals.is_contiguous()
-        if u_out is None:
-            u_out = torch.empty_like(u0)
-        tp, tobj = None, None
-        if taps:
-            tobj = HopTaps(
-                torch.zeros((self.H, B, n_slots), dtype=torch.int32, device=self.dev),
-                torch.zeros((self.H, B, n_slots), dtype=torch.float32, device=self.dev),
-                torch.zeros((self.H, B, n_slots), dtype=torch.float32, device=self.dev),
-                torch.zeros((B, self.H, self.D), dtype=torch.float32, device=self.dev),
-                torch.zeros((B, self.H, self.D), dtype=torch.float32, device=self.dev))
-            tp = abi.Taps(tobj.score_codes.data_ptr(), tobj.scores.data_ptr(), tobj.probs.data_ptr(),
-                          tobj.o.data_ptr(), tobj.u.data_ptr())
-        nbytes = int(abi.lib.qmann_hops_shared_split_packed_ws_bytes(C.byref(self.net), n_slots, B))
-        if ws is None:
-            ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=self.dev)   # (torch allocations are 16-byte aligned)
-        per_hop = vals.shape[0] == self.H
-        key_stride = n_slots * (self.Dp // 64) * nb * 8 if per_hop else 0         # one plane for several hops: tied
-        val_stride = n_slots * self.Dp if per_hop else 0
-        abi.check(abi.lib.qmann_hops_shared_split_packed(C.byref(self.net), _ptr(key_planes), key_stride, _ptr(vals), val_stride,
-                                                         n_slots, _ptr(u0), _ptr(u_out), C.byref(tp) if tp else None, B, n_slices,
-                                                         _ptr(ws), nbytes, self._s()), "qmann_hops_shared_split_packed")
+        planes = self._packed_planes(key_planes, vals, n_slots)
+        ws, nbytes = self._split_workspace(abi.lib.qmann_hops_shared_split_packed_ws_bytes, n_slots, u0.shape[0], ws)
+        r = self._hops_shared("qmann_hops_shared_split_packed", planes, n_slots, u0, taps, u_out, (n_slices, _ptr(ws), nbytes))
         self._split_ws = ws                                                       # alive until the next call: the launch is asynchronous
-        return (u_out, tobj) if taps else u_out
+        return r
 
     def hops_shared_top_packed(self, key_planes, vals, n_slots, u0, k):
         """qmann_hops_shared_top_packed: hops_shared_packed plus, per query and hop, the k most attended slots and their
         probabilities: (u_out, top_slot int32 [B][H][k], top_p float32 [B][H][k]), larger probability first, equal
         probabilities: lower slot first; entries past n_slots are slot -1 (0xFFFFFFFF), p 0.  Arguments as hops_shared_packed."""
-        B = u0.shape[0]
-        nb = key_planes.shape[-1]
-        assert vals.shape in ((self.H, n_slots, self.Dp), (1, n_slots, self.Dp))
-        assert key_planes.shape == (vals.shape[0], n_slots, self.Dp // 64, nb)
-        assert key_planes.is_contiguous() and vals.is_contiguous()
-        u_out = torch.empty_like(u0)
-        top_slot, top_p = _top_out(self.dev, B, self.H, k)
-        per_hop = vals.shape[0] == self.H
-        key_stride = n_slots * (self.Dp // 64) * nb * 8 if per_hop else 0         # one plane for several hops: tied
-        val_stride = n_slots * self.Dp if per_hop else 0
-        abi.check(abi.lib.qmann_hops_shared_top_packed(C.byref(self.net), _ptr(key_planes), key_stride, _ptr(vals), val_stride,
-                                                       n_slots, _ptr(u0), _ptr(u_out), k, _ptr(top_slot), _ptr(top_p), B,
-                                                       self._s()), "qmann_hops_shared_top_packed")
-        return u_out, top_slot, top_p
+        return self._hops_top("qmann_hops_shared_top_packed", self._packed_planes(key_planes, vals, n_slots), u0, k)
 
     def hops_shared_split_top_packed(self, key_planes, vals, n_slots, u0, k, n_slices=0):
         """qmann_hops_shared_split_top_packed: hops_shared_top_packed with the slots cut into n_slices slices (0: the library's
         choice); the workspace is allocated here, of the size hops_shared_split_packed takes.  Results as hops_shared_top_packed."""
-        B = u0.shape[0]
-        nb = key_planes.shape[-1]
-        assert vals.shape in ((self.H, n_slots, self.Dp), (1, n_slots, self.Dp))
-        assert key_planes.shape == (vals.shape[0], n_slots, self.Dp // 64, nb)
-        assert key_planes.is_contiguous() and vals.is_contiguous()
-        u_out = torch.empty_like(u0)
-        top_slot, top_p = _top_out(self.dev, B, self.H, k)
-        nbytes = int(abi.lib.qmann_hops_shared_split_packed_ws_bytes(C.byref(self.net), n_slots, B))
-        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=self.dev)       # (torch allocations are 16-byte aligned)
-        per_hop = vals.shape[0] == self.H
-        key_stride = n_slots * (self.Dp // 64) * nb * 8 if per_hop else 0
-        val_stride = n_slots * self.Dp if per_hop else 0
-        abi.check(abi.lib.qmann_hops_shared_split_top_packed(C.byref(self.net), _ptr(key_planes), key_stride, _ptr(vals),
-                                                             val_stride, n_slots, _ptr(u0), _ptr(u_out), k, _ptr(top_slot),
-                                                             _ptr(top_p), B, n_slices, _ptr(ws), nbytes, self._s()),
-                  "qmann_hops_shared_split_top_packed")
+        planes = self._packed_planes(key_planes, vals, n_slots)
+        ws, nbytes = self._split_workspace(abi.lib.qmann_hops_shared_split_packed_ws_bytes, n_slots, u0.shape[0])
+        r = self._hops_top("qmann_hops_shared_split_top_packed", planes, u0, k, (n_slices, _ptr(ws), nbytes))
         self._split_ws = ws                                                       # alive until the next call: the launch is asynchronous
-        return u_out, top_slot, top_p
+        return r
 
     def answer(self, u, answer=None, want_probs=False, serial=False):
         """serial=True: qmann_answer_f32_serial (the reference's order of additions, bit-equal logits); default: the library's
@@ -678,6 +559,16 @@ class HostModel:
         cost, match = _zero_cost_and_match(self.dev) if answer is not None else (None, None)
         return pred, cost, match
 
+    def _run(self, name, questions, answer, *args, k=None):
+        """one forward or ask of the B rows of `questions`, `name`(model, *args, B, answer, pred, cost, match[, k, top_slot,
+        top_p], stream) -> (pred, cost, match[, top_slot, top_p]); k: the call is a top form and returns the attended slots too"""
+        B = questions.shape[0]
+        pred, cost, match = self._out(B, answer)
+        top = _top_out(self.dev, B, self.cfg["n_hop"], k) if k is not None else ()
+        abi.check(getattr(abi.lib, name)(self.h, *args, B, _ptr(answer), _ptr(pred), _ptr(cost), _ptr(match),
+                                         *((k, _ptr(top[0]), _ptr(top[1])) if top else ()), self._s()), name)
+        return (pred, cost, match, *top)
+
     def last_u(self, B):
         """copy of the final hop state of the last batch, [B][D]"""
         p = abi.lib.qmann_model_last_u(self.h)
@@ -695,49 +586,25 @@ class HostModel:
         return top_idx, top_p
 
     def forward_words(self, story_words, question_words, row_off, max_slots, answer=None):
-        B = question_words.shape[0]
-        pred, cost, match = self._out(B, answer)
-        abi.check(abi.lib.qmann_model_forward_words(self.h, _ptr(story_words), story_words.shape[0], story_words.shape[1],
-                                                    _ptr(question_words), question_words.shape[1], _ptr(row_off),
-                                                    max_slots, B, _ptr(answer), _ptr(pred), _ptr(cost), _ptr(match),
-                                                    self._s()), "qmann_model_forward_words")
-        return pred, cost, match
+        return self._run("qmann_model_forward_words", question_words, answer, *_words(story_words),
+                         *_qwords(question_words), _ptr(row_off), max_slots)
 
     def forward_words_top(self, story_words, question_words, row_off, max_slots, k, answer=None):
         """qmann_model_forward_words_top: forward_words plus the attended slots of every question and hop: (pred, cost, match,
         top_slot int32 [B][H][k], top_p float32 [B][H][k]) -- rows of the question's own story, as QNet.hops_top gives them"""
-        B = question_words.shape[0]
-        pred, cost, match = self._out(B, answer)
-        top_slot, top_p = _top_out(self.dev, B, self.cfg["n_hop"], k)
-        abi.check(abi.lib.qmann_model_forward_words_top(self.h, _ptr(story_words), story_words.shape[0], story_words.shape[1],
-                                                        _ptr(question_words), question_words.shape[1], _ptr(row_off),
-                                                        max_slots, B, _ptr(answer), _ptr(pred), _ptr(cost), _ptr(match),
-                                                        k, _ptr(top_slot), _ptr(top_p), self._s()),
-                  "qmann_model_forward_words_top")
-        return pred, cost, match, top_slot, top_p
+        return self._run("qmann_model_forward_words_top", question_words, answer, *_words(story_words),
+                         *_qwords(question_words), _ptr(row_off), max_slots, k=k)
 
     def forward_words_top_float(self, story_words, question_words, row_off, max_slots, k, answer=None):
         """qmann_model_forward_words_top_float: forward_words_top for a float-attention model -- rows as QNet.hops_top_float
         gives them"""
-        B = question_words.shape[0]
-        pred, cost, match = self._out(B, answer)
-        top_slot, top_p = _top_out(self.dev, B, self.cfg["n_hop"], k)
-        abi.check(abi.lib.qmann_model_forward_words_top_float(self.h, _ptr(story_words), story_words.shape[0], story_words.shape[1],
-                                                              _ptr(question_words), question_words.shape[1], _ptr(row_off),
-                                                              max_slots, B, _ptr(answer), _ptr(pred), _ptr(cost), _ptr(match),
-                                                              k, _ptr(top_slot), _ptr(top_p), self._s()),
-                  "qmann_model_forward_words_top_float")
-        return pred, cost, match, top_slot, top_p
+        return self._run("qmann_model_forward_words_top_float", question_words, answer, *_words(story_words),
+                         *_qwords(question_words), _ptr(row_off), max_slots, k=k)
 
     def forward_shared_words(self, story_words, question_words, answer=None):
         """qmann_model_forward_shared_words: one story [n_rows][W], every question of question_words [B][Wq] attends to it"""
-        B = question_words.shape[0]
-        pred, cost, match = self._out(B, answer)
-        abi.check(abi.lib.qmann_model_forward_shared_words(self.h, _ptr(story_words), story_words.shape[0], story_words.shape[1],
-                                                           _ptr(question_words), question_words.shape[1], B, _ptr(answer),
-                                                           _ptr(pred), _ptr(cost), _ptr(match), self._s()),
-                  "qmann_model_forward_shared_words")
-        return pred, cost, match
+        return self._run("qmann_model_forward_shared_words", question_words, answer, *_words(story_words),
+                         *_qwords(question_words))
 
     def memorize_words(self, story_words):
         """qmann_model_memorize_words: embed (and for V0 / V1 models pack) the knowledge base story_words [n_rows][W] once; the
@@ -766,50 +633,24 @@ class HostModel:
 
     def ask_words(self, question_words, answer=None):
         """qmann_model_ask_words: every question of question_words [B][Wq] attends to the memorised knowledge base"""
-        B = question_words.shape[0]
-        pred, cost, match = self._out(B, answer)
-        abi.check(abi.lib.qmann_model_ask_words(self.h, _ptr(question_words), question_words.shape[1], B, _ptr(answer),
-                                                _ptr(pred), _ptr(cost), _ptr(match), self._s()), "qmann_model_ask_words")
-        return pred, cost, match
+        return self._run("qmann_model_ask_words", question_words, answer, *_qwords(question_words))
 
     def ask_words_top(self, question_words, k, answer=None):
         """qmann_model_ask_words_top: ask_words plus the attended slots of every question and hop: (pred, cost, match,
         top_slot int32 [B][H][k], top_p float32 [B][H][k]) -- rows of the memorised story, as QNet.hops_shared_top gives them"""
-        B = question_words.shape[0]
-        pred, cost, match = self._out(B, answer)
-        top_slot, top_p = _top_out(self.dev, B, self.cfg["n_hop"], k)
-        abi.check(abi.lib.qmann_model_ask_words_top(self.h, _ptr(question_words), question_words.shape[1], B, _ptr(answer),
-                                                    _ptr(pred), _ptr(cost), _ptr(match), k, _ptr(top_slot), _ptr(top_p),
-                                                    self._s()), "qmann_model_ask_words_top")
-        return pred, cost, match, top_slot, top_p
+        return self._run("qmann_model_ask_words_top", question_words, answer, *_qwords(question_words), k=k)
 
     def ask_words_top_packed(self, question_words, k, answer=None):
         """qmann_model_ask_words_top_packed: ask_words_top for a Hamming V0 / V1 model -- (pred, cost, match, top_slot int32
         [B][H][k], top_p float32 [B][H][k]), rows of the memorised story as QNet.hops_shared_top_packed gives them"""
-        B = question_words.shape[0]
-        pred, cost, match = self._out(B, answer)
-        top_slot, top_p = _top_out(self.dev, B, self.cfg["n_hop"], k)
-        abi.check(abi.lib.qmann_model_ask_words_top_packed(self.h, _ptr(question_words), question_words.shape[1], B, _ptr(answer),
-                                                           _ptr(pred), _ptr(cost), _ptr(match), k, _ptr(top_slot), _ptr(top_p),
-                                                           self._s()), "qmann_model_ask_words_top_packed")
-        return pred, cost, match, top_slot, top_p
+        return self._run("qmann_model_ask_words_top_packed", question_words, answer, *_qwords(question_words), k=k)
 
     def ask_words_top_float(self, question_words, k, answer=None):
         """qmann_model_ask_words_top_float: ask_words_top for a float-attention model with float asks enabled -- (pred, cost,
         match, top_slot int32 [B][H][k], top_p float32 [B][H][k]), rows of the memorised story as QNet.hops_shared_top_float
         gives them"""
-        B = question_words.shape[0]
-        pred, cost, match = self._out(B, answer)
-        top_slot, top_p = _top_out(self.dev, B, self.cfg["n_hop"], k)
-        abi.check(abi.lib.qmann_model_ask_words_top_float(self.h, _ptr(question_words), question_words.shape[1], B, _ptr(answer),
-                                                          _ptr(pred), _ptr(cost), _ptr(match), k, _ptr(top_slot), _ptr(top_p),
-                                                          self._s()), "qmann_model_ask_words_top_float")
-        return pred, cost, match, top_slot, top_p
+        return self._run("qmann_model_ask_words_top_float", question_words, answer, *_qwords(question_words), k=k)
 
     def forward_bow(self, story, question, row_off, max_slots, answer=None):
-        B = question.shape[0]
-        pred, cost, match = self._out(B, answer)
-        abi.check(abi.lib.qmann_model_forward_bow(self.h, _ptr(story), story.shape[0], _ptr(question), _ptr(row_off),
-                                                  max_slots, B, _ptr(answer), _ptr(pred), _ptr(cost), _ptr(match),
-                                                  self._s()), "qmann_model_forward_bow")
-        return pred, cost, match
+        return self._run("qmann_model_forward_bow", question, answer, _ptr(story), story.shape[0], _ptr(question), _ptr(row_off),
+                         max_slots)
