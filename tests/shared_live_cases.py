@@ -18,6 +18,8 @@ negative the hot rows are aligned AGAINST u.  Three repairs run per plane until 
 another query (or carries a quarter of the weight of that query's weakest hot row) is re-drawn on a random 60 % of the columns,
 a cold row that does so gets a zero key, and a p on a truncation step gets one warm row of the query's own
 (live_hops_cases.NUDGES).  A tied memory (one plane for every hop) is planted in repeated passes over the hops.
+plant_shared also takes the Hamming modes (mode, num_bit: shared_ham_live_cases.py); the fixed-point cases below come out byte
+for byte as without them (test_shared_ham_live_inputs.py holds their digests).
 
 NATIVE Q2.5 ATTENTION.  The top score is 3.97, e^3.97 = 53, and a cold row scores about 0 (e^0 = 1).  A hot row among n_hot tied
 ones survives Q2.5 only while 53 / (n_hot . 53 + S) >= 1/32, i.e. S <= 53 . (32 - n_hot): about 1 500 slots.  Longer memories
@@ -120,10 +122,40 @@ def _score(oracle, cfg, h, key, u_att):
     return float(oracle.dot_mat_vec_fwd((key / float(1 << fa)).astype(np.float32)[None], u_att, False, True, (ia, fa), fb)[0])
 
 
+def _hot_key_ham(oracle, cfg, h, u_att, delta):
+    """the Hamming modes' hot key, as int8 codes on the attention grid.  It is built on the BYTE the kernels compare -- the top
+    byte of the oracle's own sign-magnitude word of u (qo_float2fixed at frac = 31 - iwl_att), so that a hop input on a finer grid
+    than the attention's, a saturated column and a small negative column (sign set, magnitude 0: the word's minus zero) are what
+    the oracle reads.  delta: the sign of round(delta) columns turned, each one step of the score under the top; a pair (flips,
+    fine): `fine` score CODES besides, through compared magnitude bits of further columns (V0: one bit a code; V1: bit i of
+    num_bit counts 2^(num_bit - 1 - i) codes of 2^-num_bit).  A hop with a negative attention scale gets the key that agrees with
+    u in NOTHING the mode counts, so that its score is the lowest there is and its scaled score the largest: V0 -- every compared
+    bit (the sign and the top num_bit - 1 magnitude bits) turned; V1 -- the sign turned and the magnitude kept (the column counts
+    -sum 2^-(i+1) in full).  The byte 0x80 is the code -128, the float -2^iwl_att, which the oracle reads as minus zero too
+    (test_gpu_batch.ham_key_bytes)."""
+    ia, nb = cfg["fmt_att"][h][0], cfg["num_bit"]
+    byte = (oracle.float2fixed(u_att, ia, 31 - ia).view(np.uint32) >> 24).astype(np.int64)
+    flips, fine = delta if isinstance(delta, tuple) else (int(round(delta)), 0)
+    byte[:flips] ^= 0x80
+    col = flips                                           # `fine`: compared magnitude bits turned in the columns behind, heaviest first
+    for i in range(1, nb):
+        w = 1 if cfg["attention_mode"] == 10 else 1 << (nb - 1 - i)
+        while fine >= w:
+            byte[col] ^= 0x80 >> i
+            col, fine = col + 1, fine - w
+    sc = cfg.get("att_scale")
+    if sc is not None and sc[h] < 0:
+        byte ^= (0xFF << (8 - nb)) & 0xFF if cfg["attention_mode"] == 10 else 0x80
+    return np.where(byte == 0x80, -128, np.where(byte & 0x80, -(byte & 0x7F), byte & 0x7F))
+
+
 def _hot_key(oracle, cfg, h, u_att, delta, cols=None):
     """the key of a hot row for the hop input u_att: the smallest amplitude whose own score reaches the top code, on `cols`
     (default: every column); delta > 0: live_hops_cases._hot_key_fixed from that amplitude, `delta` under the top.  A hop with a
-    negative attention scale gets the key aligned AGAINST u (its scaled score is then the largest)."""
+    negative attention scale gets the key aligned AGAINST u (its scaled score is then the largest).  Hamming modes: _hot_key_ham
+    (`cols` plays no part: a key thinned by columns would leave its pair's tie)."""
+    if cfg["attention_mode"] != 2:
+        return _hot_key_ham(oracle, cfg, h, u_att, delta)
     ia, fa = cfg["fmt_att"][h]
     full = min((1 << (ia + fa)) - 1, 127)
     top = full / float(1 << fa)
@@ -135,8 +167,10 @@ def _hot_key(oracle, cfg, h, u_att, delta, cols=None):
 
 def plant_shared(oracle, name, S, D, B, H=3, fmt=Q52, fmt_att=None, fmt_w=None, fmt_bin=None, cfg_extra=None, tied=False, deltas=TIED,
                  n_hot=None, must=(), sigma_cold=2.0, density=0.15, sigma_v=14.0, v_min=6, sigma_u=8.0, lin_density=0.5, min_live=3,
-                 envs=({},), qts=(None, 4), slices=(2, 3, 7), passes=1, copies=False, c5=False, rounds=16):
-    """One shared memory.  deltas (or deltas(q)): one hot row per entry, its score that far under the top (n_hot(q): so many tied
+                 envs=({},), qts=(None, 4), slices=(2, 3, 7), passes=1, copies=False, c5=False, rounds=16, mode=2, num_bit=8):
+    """One shared memory.  mode, num_bit: the attention (2: fixed point; 10 / 11: Hamming V0 / V1 on the top num_bit bits of the key
+    bytes -- shared_ham_live_cases.py; `deltas` then count sign flips under the top, and the cold rows are dense random codes).
+    deltas (or deltas(q), deltas(q, h)): one hot row per entry, its score that far under the top (n_hot(q) or n_hot(q, h): so many tied
     rows instead).
     must: rows dealt out to the (hop, query) pairs first.  passes: planting passes over the hops (a tied memory takes several)."""
     seed = zlib.crc32(name.encode())
@@ -144,12 +178,12 @@ def plant_shared(oracle, name, S, D, B, H=3, fmt=Q52, fmt_att=None, fmt_w=None, 
     fmt = [tuple(fmt)] * H if isinstance(fmt[0], int) else [tuple(f) for f in fmt]
     fmt_att = [tuple(f) for f in (fmt_att or fmt)]
     fmt_w = [tuple(f) for f in (fmt_w or fmt_att)]
-    cfg = dict(n_hop=H, dim_emb=D, dim_input=4, attention_mode=2, softmax_variant=0, f_fixed=True, en_lin_map=True, fmt=fmt,
-               fmt_w=fmt_w, fmt_att=fmt_att, fmt_bin=tuple(fmt_bin or fmt_att[0]), num_bit=8)
+    cfg = dict(n_hop=H, dim_emb=D, dim_input=4, attention_mode=mode, softmax_variant=0, f_fixed=True, en_lin_map=True, fmt=fmt,
+               fmt_w=fmt_w, fmt_att=fmt_att, fmt_bin=tuple(fmt_bin or fmt_att[0]), num_bit=num_bit)
     cfg.update(cfg_extra or {})
     P = 1 if tied else H
     assert not tied or (len(set(fmt)) == 1 and len(set(fmt_att)) == 1), "a tied plane is read on one grid"
-    keys, vals = lc.cold_memory(rng, P, S, D, 2, fmt_att, fmt, sigma_cold, density, sigma_v)
+    keys, vals = lc.cold_memory(rng, P, S, D, mode, fmt_att, fmt, sigma_cold, density, sigma_v)
     wts = dict(w_ans=np.zeros((4, D), np.float32))
     if cfg["en_lin_map"]:
         wts["w_h"] = lc.linear_maps(rng, H, D, fmt_w, lin_density)
@@ -159,7 +193,8 @@ def plant_shared(oracle, name, S, D, B, H=3, fmt=Q52, fmt_att=None, fmt_w=None, 
 
     # rows: `must` dealt round the pairs, the rest from one shuffle per plane; no row of a plane serves two pairs
     pairs = [(h, q) for h in range(H) for q in range(B)]
-    dls = {(h, q): (0,) * n_hot(q) if n_hot else tuple(deltas(q) if callable(deltas) else deltas) for h, q in pairs}
+    per = lambda f, q, h: f(q, h) if f.__code__.co_argcount == 2 else f(q)          # (a callable of the query, or of query and hop)
+    dls = {(h, q): (0,) * per(n_hot, q, h) if n_hot else tuple(per(deltas, q, h) if callable(deltas) else deltas) for h, q in pairs}
     hot = {pr: [] for pr in pairs}
     for j, r in enumerate(dict.fromkeys(must)):
         for i in range(len(pairs)):
@@ -222,8 +257,10 @@ def plant_shared(oracle, name, S, D, B, H=3, fmt=Q52, fmt_att=None, fmt_w=None, 
                 if kind == "foreign":
                     oh, oq, oi = x
                     put(oh, oq, oi, u_att, cols=np.nonzero(rng.random(D) < 0.6)[0])
-                elif kind == "cold":
+                elif kind == "cold" and mode == 2:
                     keys[x[0], x[1], :D] = 0
+                elif kind == "cold":                            # (Hamming: a zero key is no cold one; another random row)
+                    keys[x[0], x[1], :D] = np.clip(np.rint(rng.normal(0, 40, D)), -127, 127)
                 else:
                     pr = (h, x)
                     if pr not in warm:
