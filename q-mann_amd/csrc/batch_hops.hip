@@ -30,9 +30,11 @@
 //
 //   1b. (the STOP instantiation: e^x softmax, no taps, a bound some hop can reach -- hops_host.h::scan_stop_gate)  While it
 //      scans, the workgroup also sums e^(x_r - Xb) over the rows retired so far, Xb the largest score the attention format
-//      can hold.  Once that sum passes 2^frac (1 + 2^-6) every read-out weight of the hop is known to quantise to code 0
+//      can hold, and credits every row NOT yet read with the least it can weigh, f = e^(Xmin - Xb), Xmin the smallest such
+//      score.  Once the two together pass 2^frac (1 + 2^-6) every read-out weight of the hop is known to quantise to code 0
 //      whatever the unread rows hold (derivation: ScanStop below): the wavefronts leave the scan, steps 2 and 3 are skipped
-//      and the hop continues with o = 0, the result the full scan would have produced.  This scan works in units of
+//      and the hop continues with o = 0, the result the full scan would have produced.  (Kept as one word: the retired rows'
+//      e^(x_r - Xb) - f against the threshold less S f.  Where S f alone passes it, no row is read at all.)  This scan works in units of
 //      two loads per lane (half a tile), three per wavefront -- one being retired, two in flight: the lanes that retire
 //      a unit's rows add the rows' terms to the workgroup's sum, THEN the wavefront looks at that sum (its own unit included),
 //      and only then asks for another unit.
@@ -56,6 +58,36 @@ namespace {
 // 153 472 . 2^-24 = 0.92 %: the threshold 2^frac (1 + 2^-6) leaves 1.5 %, so a sum that passes it stands for a true one above
 // 2^frac (1 + 0.6 %), which also puts 1 / total far enough below 2^-frac that the float quotient cannot round up to it.  A NaN
 // or infinite scale makes the sum NaN, which never compares >= thr: such a hop runs the full path.
+// The unread rows' floor.  An unread row is not worth nothing: its clamped code lies in [-maxm, +maxm], so its score is at least
+// Xmin = min(sm_scaled(+top), sm_scaled(-top)), and with f = e^(Xmin - Xb), over the S rows the softmax runs over (S clipped to
+// max_slots: rows beyond it are no part of the softmax and earn nothing),
+//     total >= sum_{r in P} e^(x_r - Xb) + (S - |P|) f.
+// The kernel holds a float f_dev <= f, adds the NET term e_r - f_dev per retired row and compares the word with
+// thr' = thr - S f_dev: word >= thr' says exactly sum_P e_r + (S - |P|) f_dev >= thr.  f_dev is formed once per hop from the very
+// sequence the retire hook uses, raw = exp2(fma(code_min, stop_k1, stop_k0)) at the code of the smaller score (-maxm, or +maxm
+// for a negative scale layer: the sign of stop_k1), as raw (1 - 2^-12) where raw >= kFloorMin = 2^-100, else 0.  Two facts carry
+// the proof:
+//   (a) f_dev <= e^(Xmin - Xb) exactly.  The FMA's argument is off from (Xmin - Xb) log2 e by < 4e-5 (three float roundings and
+//       the constant's, on a magnitude of at most 100 + 1), which moves 2^arg by < 3e-5 relative; v_exp_f32 adds 1 ulp (1.2e-7),
+//       the derating product 2^-24: together far inside the 2^-12 = 2.4e-4 taken off.
+//   (b) f_dev <= every value the retire hook can compute, for any code.  Not because v_exp_f32 were monotone -- nothing here
+//       assumes that: a correctly rounded FMA IS monotone in the code (stop_k1, stop_k0 fixed), so every code's argument is >=
+//       code_min's, arg_min; the instruction is good to 1 ulp, so every computed e_r >= 2^arg_min (1 - 2^-22) while raw <=
+//       2^arg_min (1 + 2^-22), and (1 + 2^-22) (1 - 2^-12) < 1 - 2^-22.  That needs results no 1-ulp bound fails for: with
+//       raw >= 2^-100 every e_r is a normal float far above 2^-126.  Where raw is smaller -- a float denormal or 0 is the
+//       case, and there a row's own term may flush to 0 -- f_dev = 0: the credit vanishes and the hop is the plain bound's.
+// By (b) every net term is >= 0 (a float difference of a >= b is never negative), and an added non-negative float never lowers
+// the word: "the sum only grows" below still holds.  It has to: a wavefront that left early has not scored its rows, and a word
+// that could sink below thr' again would send the workgroup into the softmax over an incomplete score array.
+// The error budget for this sum: each net term carries one more rounding (2^-24 relative to itself, as the term's v_exp_f32
+// does), the additions as above at most 153 472 . 2^-24 = 0.92 % -- relative to a word that is now SMALLER than the plain sum --
+// and S f_dev and thr - S f_dev round within 2^-23 of thr together, while (a) keeps the credit itself low by 2e-4 of its size:
+// a word that passes thr' stands for sum_P e_r + (S - |P|) f above thr (1 - 0.93 %) = 2^frac (1 + 0.6 %), as before.  The
+// threshold, its 1.5 % and Xb are unchanged.
+// When S f_dev alone reaches thr (thr' <= 0: a scale layer that narrows the score range, or 91 000 rows and more at Q2.5) the
+// hop is settled before a row is read: the kernel skips the scan -- no request, no retire, no flush -- and the comparison all
+// threads make anyway, word = 0 >= thr', says "zero".  A NaN or infinite scale makes raw NaN, which fails raw >= kFloorMin: f_dev
+// = 0, thr' = thr, and the NaN sum runs the full path as before; S = 0 keeps thr' = thr > 0.
 // Adding and looking (hops_common.h::scan_rows_stop looks once per unit, behind the unit's retiring).  add(): the lane that
 // retires a row adds the row's term to one LDS float (ds_add_f32: nothing returned, nothing waited for; the lanes of one
 // instruction that hit the one address are serialised by the LDS, not by the wavefront -- no cross-lane reduction, no VALU
@@ -73,8 +105,11 @@ struct ScanStop {
     // 256, 32 at 64), and units per wavefront -- one being retired, kDepth - 1 in flight
     static constexpr int kUnitLoads = 2;
     static constexpr int kDepth = 3;
-    float *word;              // the workgroup's sum (LDS)
-    float thr;
+    // the unread rows' floor (above): what is taken off the raw value, and the smallest raw value that earns a credit at all
+    static constexpr float kFloorDerate = 1.0f - 0x1p-12f;
+    static constexpr float kFloorMin = 0x1p-100f;
+    float *word;              // the workgroup's sum of net terms (LDS)
+    float thr;                // thr' = thr - S f_dev
     // One retired row's e^(x_r - Xb) joins the workgroup's sum: the lane that retires the row adds it (ds_add_f32: nothing
     // returned, nothing waited for).  Written out: as an atomicAdd the compiler wraps it in its loop over the active lanes.
     // The compiler's wait counting cannot see this instruction.  Inside the scan that is harmless: LDS operations complete
@@ -146,19 +181,25 @@ k_hops_fixed(const HopArgs a, const StoryTop<TOP> tp)
         if (tid == 0) misc[0] = 0u;
         // the bound of step 1b: e^(x - Xb) = 2^(code . stop_k1 + stop_k0)
         float *stop_word = (float *)(misc + 1);
-        float stop_thr = 0.0f, stop_k1 = 0.0f, stop_k0 = 0.0f;
+        float stop_thr = 0.0f, stop_k1 = 0.0f, stop_k0 = 0.0f, stop_f = 0.0f;
         if constexpr (STOP) {
             const SmCfg smc = sm_cfg(a, h);
             const float top = qm_scale_down((float)maxm, fm.frac), log2e = 1.44269504f;
             const float xb = fmaxf(sm_scaled(top, smc), sm_scaled(-top, smc));
             stop_k1 = sm_scaled(qm_scale_down(1.0f, fm.frac), smc) * log2e;
             stop_k0 = -xb * log2e;
-            stop_thr = (float)(1u << fa.frac) * (1.0f + 0.015625f);
+            // the floor f_dev (ScanStop): the retire hook's own sequence at the code of the smallest score (a negative scale
+            // layer swaps the ends; a NaN compares false throughout and leaves f_dev = 0), derated, 0 below kFloorMin
+            const float raw = __builtin_amdgcn_exp2f(__builtin_fmaf(stop_k1 >= 0.0f ? (float)-maxm : (float)maxm, stop_k1, stop_k0));
+            stop_f = raw >= ScanStop::kFloorMin ? raw * ScanStop::kFloorDerate : 0.0f;
+            // thr' = thr - S f_dev: the S rows of this query the softmax runs over (S is clipped to max_slots above)
+            stop_thr = (float)(1u << fa.frac) * (1.0f + 0.015625f) - (float)S * stop_f;
             if (tid == 0) stop_word[0] = 0.0f;
         }
         __syncthreads();
 
-        if (S > 0) {
+        // (STOP, thr' <= 0: the floor alone settles the hop -- no request, no retire, no flush; the word stays 0 >= thr')
+        if (S > 0 && !(STOP && stop_thr <= 0.0f)) {
             // lane constants: |u| pre-shifted so that saturation == the per-product clamp
             ScanConst c;
             uint32_t sh = 0;
@@ -171,7 +212,7 @@ k_hops_fixed(const HopArgs a, const StoryTop<TOP> tp)
                 const int code = v > maxm ? maxm : (v < -maxm ? -maxm : v);
                 sc[r] = (int8_t)code;
                 atomicAdd(&hw[code + 127], 1u);
-                if constexpr (STOP) ScanStop::add(stop_word, __builtin_amdgcn_exp2f(__builtin_fmaf((float)code, stop_k1, stop_k0)));
+                if constexpr (STOP) ScanStop::add(stop_word, __builtin_amdgcn_exp2f(__builtin_fmaf((float)code, stop_k1, stop_k0)) - stop_f);   // the net term, >= 0
             };
             if (S < (kWave / LPR) * kUnroll) scan_rows_short<LPR>(kb, S, row_sum, retire, lane, wave, nwaves);
             else if (STOP || nwaves == kWaves) {        // (a stopping launch always has four wavefronts)

@@ -114,6 +114,9 @@ inline bool shared_no_queries(uint32_t n_query, int &rc)
 // memory at all: a hop's scan sums e^(x_r - Xb) <= 1 per row and stops at 2^frac (1 + 2^-6), so even a memory of all-zero scores
 // (e^x = 1) needs 2^frac . e^Xb . (1 + 2^-6) rows.  Xb as the kernel forms it (one float product for the scale layer), the rest
 // in double; a NaN scale compares false.  Q2.5 wants 1 720 rows, Q5.2 4 e^31.75: such a launch keeps the plain kernel.
+// The kernel's credit for unread rows (ScanStop: each at least f = e^(Xmin - Xb)) leaves this decision as it is: a memory of all-zero
+// scores read to the end reaches that bound within max_slots exactly when max_slots . e^(-Xb) >= thr, the test below -- the
+// floor only moves the row at which a reachable bound is reached, or (S f >= thr) settles the hop unread, and S f <= S e^(-Xb).
 inline bool scan_stop_gate(const HopArgs &a, uint32_t max_slots)
 {
     if (a.tap_codes || a.tap_scores || a.tap_probs || a.tap_o || a.tap_u) return false;
