@@ -388,7 +388,7 @@ int qmann_hops_shared_split_top_packed(const qmann_net *net, const uint64_t *key
  * Arithmetic.  qmann_answer_f32_serial sums every logit over the embedding axis serially in float, separate multiply and add:
  * the reference's own order (lib/layer_cuda.cu:70-80), bit-equal logits; e^x through expf, a double total, the quotient of the
  * double division (:2006-2042).  qmann_answer_f32 takes, at the bAbI shapes (dim_emb <= 64, dim_input <= 256, e^x / 2^x base),
- * the FUSED form on the bf16 matrix cores instead (csrc/batch_answer.hip::k_answer_mfma): u -- which must lie on an 8-bit grid, as
+ * the FUSED form on the bf16 matrix cores instead (csrc/answer_fused.h::k_answer_mfma): u -- which must lie on an 8-bit grid, as
  * the hop kernels write it -- times W split exactly into three bf16 parts, float accumulation, hardware 2^x; closer to the
  * exact sum than the serial float loop, and within north_star's 1e-5 of it on the probabilities (absolute; relative 1e-5 while
  * |logit| <= 16, where a unit in the last place of a logit is still below 1e-6); predictions agree wherever the two best
@@ -408,7 +408,7 @@ int qmann_answer_f32_serial(const qmann_net *net, const float *w_ans, const floa
  * probs[q][top_idx[q][j]], and row q lists the k entries of probs[q][:] that come first in the order "larger probability first,
  * equal probabilities: higher index first" -- the tie rule of pred (lib/layer_cuda.cu:1918-1939), so top_idx[q][0] is the serial
  * call's pred[q] always, also among probabilities that underflowed to 0.  Every softmax base.  The kernels are the serial-order
- * ones of the shape with k rounds of their arg-max reduction behind the quotients (csrc/batch_answer.hip); the fused bf16 form
+ * ones of the shape with k rounds of their arg-max reduction behind the quotients (csrc/answer_serial.h); the fused bf16 form
  * has no ranked build; qmann_answer_i8's int8 matrices have one of their own, qmann_answer_topk_i8 below.
  * One ordered step on `stream`, no allocation, no library scratch, no second stream: it can be captured in a graph.
  * Nothing is launched and the code returned is: QMANN_EINVAL for null pointers, k = 0, k > QMANN_MAX_TOPK, k > dim_input,

@@ -1,4 +1,4 @@
-"""The float answer layer on the bf16 matrix cores (csrc/batch_answer.hip::k_answer_mfma: the default of qmann_answer_f32 at the bAbI
+"""The float answer layer on the bf16 matrix cores (csrc/answer_fused.h::k_answer_mfma: the default of qmann_answer_f32 at the bAbI
 shapes) against the serial-order kernels (QMANN_ANSWER_EXACT: bit-equal to the reference's loop, lib/layer_cuda.cu:70-80) and
 against a float64 softmax of the exact logits.  north_star grants the float softmax 1e-5; the criteria are those of
 test_gpu_batch.py::run_case: probabilities within rtol 1e-5 / atol 1e-7, predictions equal wherever the top-2 gap exceeds 1e-6."""

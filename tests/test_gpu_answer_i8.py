@@ -1,4 +1,4 @@
-"""qmann_answer_i8 (csrc/batch_answer.hip: k_answer_i8_part + k_answer_i8_combine, the one-pass form; k_logits_mfma_i8 +
+"""qmann_answer_i8 (csrc/answer_i8.h: k_answer_i8_part + k_answer_i8_combine, the one-pass form; k_logits_mfma_i8 +
 k_answer<true>, the two-kernel form) against the exact integer reference of answer_i8_cases.py, case by case: every byte format
 pair, every width class and the scalar-load branch, dictionaries from 1 answer to 13 slices, the batch edges of the 16-query
 tile and the 64-query workgroup, the second trips of the three grid-stride loops, u off the grid and beyond its range, labels

@@ -1,4 +1,4 @@
-"""qmann_answer_topk_i8 (csrc/batch_answer.hip: the ranked builds of k_answer_i8_part and k_answer<true>, k_answer_i8_combine_topk)
+"""qmann_answer_topk_i8 (csrc/batch_answer_i8.hip: the ranked builds of k_answer_i8_part and k_answer<true>, k_answer_i8_combine_topk)
 against the integer reference of answer_topk_i8_cases.py.
 
 top_idx is compared exactly at every softmax base a case lists; nothing is excused.  top_p: in the one-pass form (bases 0 and 1)

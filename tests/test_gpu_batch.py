@@ -51,7 +51,7 @@ E2E_FLOAT_EXCUSED = 2              # the whole forward in mode 1 against the ora
 
 
 def check_fused_probs(got, want, logits, what=""):
-    """The FUSED float answer layer (qmann_answer_f32's default at the bAbI shapes: bf16 matrix cores, csrc/batch_answer.hip::
+    """The FUSED float answer layer (qmann_answer_f32's default at the bAbI shapes: bf16 matrix cores, csrc/answer_fused.h::
     k_answer_mfma) against the oracle's probabilities `want` of one query.  north_star grants the float softmax 1e-5: absolute
     1e-5 always; relative 1e-5 (+ 1e-7) -- the criterion of the serial form -- while a unit in the last place of the logits is
     below 1e-6 (|logit| < 8), scaled up with that unit beyond: two correct float evaluations of sum_c w u differ by units in the

@@ -155,7 +155,7 @@ def test_no_quad_long(env, monkeypatch):
 
 @pytest.mark.parametrize("D,V,B,sig", [(60, 30, 5, 40), (256, 4096, 300, 12), (60, 4097, 2000, 1)])
 def test_answer_two_pass(env, monkeypatch, D, V, B, sig):
-    """batch_answer.hip: qmann_answer_i8 without a probabilities output and with a true exponential runs in one pass unless
+    """batch_answer_i8.hip: qmann_answer_i8 without a probabilities output and with a true exponential runs in one pass unless
     QMANN_ANSWER_TWO_PASS.  Predictions and the match count are equal; the cost is held to the criterion of
     test_gpu_batch.py::test_answer_mfma_i8_one_pass (rel 1e-4, abs 1e-6): two float sums over the batch in different orders
     cannot agree bit for bit."""

@@ -19,5 +19,13 @@ done
 rc=0
 norm() { grep -v '^\s*\.file\|^\s*\.ident\|\.loc\b' $1 | sed 's/__hip_cuid_[0-9a-f]*/__hip_cuid_X/g'; }    # (the compilation-unit id hashes the whole source text)
 # (a DIFFERENT unit is listed kernel by kernel; KEEP=1 leaves the .s files of both sides in place for a closer look)
-for s in $T/A/*.s; do b=$(basename $s); if cmp -s <(norm $s) <(norm $T/B/$b); then echo "same      $b"; else echo "DIFFERENT $b"; rc=1; python3 $R/tools/device_asm_kernels.py $s $T/B/$b | sed 's/^/    /'; fi; done
+# A unit that B split or renamed is followed: its kernels are looked up in ALL of B's units (their names carry no file name), and
+# it reads MOVED when each is the same where it went.  Last, the kernels that B has and no unit of A: an instantiation B added.
+for s in $T/A/*.s; do
+  b=$(basename $s)
+  if [ -f $T/B/$b ] && cmp -s <(norm $s) <(norm $T/B/$b); then echo "same      $b"; continue; fi
+  if out=$(python3 $R/tools/device_asm_kernels.py $s $T/B/*.s); then echo "MOVED     $b"; else echo "DIFFERENT $b"; rc=1; fi
+  echo "$out" | sed 's/^/    /'
+done
+if ! out=$(python3 $R/tools/device_asm_kernels.py --only-b <(cat $T/A/*.s) $T/B/*.s); then echo "NEW IN B"; echo "$out" | sed 's/^/    /'; rc=1; fi
 if [ -n "$KEEP" ]; then echo "kept: $T/A $T/B"; else rm -rf $T; fi; exit $rc
